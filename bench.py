@@ -13,7 +13,13 @@ exchange_sender_node.h:228-235), every rank merging its key-hash shard in
 parallel.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--config NAME]
+                       [--dump-outputs DIR] [--full]
 The driver launches N>1 via torch.distributed.run; ranks read RANK/WORLD_SIZE.
+
+A plain run sets up, warms up, times the K steps and prints the result line.
+--dump-outputs DIR also writes what the last timed step computed (rank 0) as
+DIR/<name>.npy. --full adds the legs the headline figure does not need (the
+CPU baseline on the host cores).
 """
 import argparse
 import json
@@ -160,6 +166,43 @@ def cpu_baseline_leg(cfg, sample_rows):
             "sample": f"{sample_rows} rows of the same workload, {dt:.1f}s"}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # a dump stays well under 64 MB in all
+
+
+def agg_outputs(res, cfg):
+    """What a caller of filter_agg receives (AggResult.fetch in canonical key
+    order), as float64 arrays: counts and this workload's int64 sums are
+    exact in a double, the encoded u64 keys go out as exact 32-bit halves.
+    A result too large for the budget is sampled at a fixed seeded set of
+    group positions, so two builds dump the same groups."""
+    import numpy as np
+    got = res.fetch(sorted=True)
+    n, na, ng = got["ngroups"], len(cfg["aggs"]), len(cfg["group"])
+    m = min(n, DUMP_BUDGET_BYTES // (8 * (2 + 2 * ng + 2 * na)))
+    sel = np.arange(n) if m == n else \
+        np.sort(np.random.default_rng(SEED).choice(n, size=m, replace=False))
+    # each aggregate's value lives in the int64 or the double lane by type
+    agg = np.empty((na, m), dtype=np.float64)
+    for a, (fn, col) in enumerate(cfg["aggs"]):
+        is_d = fn == "avg" or (fn in ("sum", "min", "max")
+                               and cfg["specs"][col][0] == TYPE_DOUBLE)
+        agg[a] = (got["agg_d"] if is_d else got["agg_i"])[a][sel]
+    enc = got["enc"][sel, :ng]
+    return {"ngroups": [n], "rows_passed": [got["rows_passed"]],
+            "group_index": sel, "flags": got["flags"][sel],
+            "key_hi": enc >> np.uint64(32),
+            "key_lo": enc & np.uint64(0xFFFFFFFF),
+            "agg": agg, "agg_has": got["agg_has"][:, sel]}
+
+
+def dump_outputs(out_dir, arrays):
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"),
+                np.asarray(a).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -168,7 +211,14 @@ def main():
     ap.add_argument("--config", default="config3_1e9_mixed")
     ap.add_argument("--rows", type=int, default=0, help="override rows per GPU")
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline figure does not "
+                         "need (CPU baseline)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -185,13 +235,8 @@ def main():
         dist = tdist
         torch.cuda.set_device(local_rank)
 
-    # pin clocks: the box's DVFS governor drops to ~100 MHz between steps and
-    # ramps slowly, making otherwise-identical steps bimodal (measured in
-    # profiles/; junction temps ~46C, nowhere near thermal limits)
-    if local_rank == 0:
-        import subprocess
-        subprocess.run(["rocm-smi", "--setperflevel", "high"],
-                       capture_output=True, check=False)
+    # device clocks and power settings are left as the machine has them: a
+    # benchmark must not change a setting other jobs share
 
     from baikaldb_amd import GpuEngine, QueryPlan
     eng = GpuEngine(device=local_rank)
@@ -211,8 +256,12 @@ def main():
 
     is_sort = "order" in cfg
 
-    def one_sort_step(timed_kernels):
+    kept = {}  # the last timed step's result, held for --dump-outputs
+
+    def one_sort_step(timed_kernels, keep):
         rowids = eng.sort_topk(t, cfg["order"], cfg["limit"], plan=plan)
+        if keep:
+            kept["rowids"] = rowids
         if timed_kernels is not None:
             timed_kernels.append(eng.topk_kernel_ms())
         if dist is not None:
@@ -245,9 +294,9 @@ def main():
             torch.cuda.synchronize()
         return len(rowids), 0
 
-    def one_step(timed_kernels):
+    def one_step(timed_kernels, keep=False):
         if is_sort:
-            return one_sort_step(timed_kernels)
+            return one_sort_step(timed_kernels, keep)
         res = eng.filter_agg(t, plan, expected_groups=cfg["expected_groups"])
         if timed_kernels is not None:
             timed_kernels.append(res.kernel_ms)
@@ -307,11 +356,17 @@ def main():
                 log(f"[dbg] exchange merge leg {(time.perf_counter()-t_x0)*1e3:.1f} ms")
             rp = res.rows_passed
             ng = int(tot.item())
-            res.free()
+            if keep:
+                kept["res"] = res
+            else:
+                res.free()
             return rp, ng
         rp = res.rows_passed
         ng = res.ngroups
-        res.free()
+        if keep:
+            kept["res"] = res
+        else:
+            res.free()
         return rp, ng
 
     log(f"[bench] warmup x{args.warmup}")
@@ -325,9 +380,10 @@ def main():
     dbg = os.environ.get("BK_BENCH_DEBUG")
     kms = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    dump_rank0 = bool(args.dump_outputs) and rank == 0
+    for step in range(args.steps):
         s0 = time.perf_counter()
-        rp, ng = one_step(kms)
+        rp, ng = one_step(kms, keep=dump_rank0 and step == args.steps - 1)
         if dbg:
             log(f"[dbg] step wall {(time.perf_counter()-s0)*1e3:.1f} ms, "
                 f"kernels {kms[-1] if kms else 0:.1f} ms")
@@ -350,6 +406,15 @@ def main():
     if rank != 0:
         return
 
+    if args.dump_outputs:
+        if is_sort:
+            arrays = {"rowids": kept["rowids"]}
+        else:
+            arrays = agg_outputs(kept["res"], cfg)
+            kept["res"].free()
+        dump_outputs(args.dump_outputs, arrays)
+        log(f"[bench] wrote {len(arrays)} output arrays to {args.dump_outputs}")
+
     # roofline of the dominant kernel (fused filter+agg), HIP-event timed on
     # its launch stream inside libbkgpu (bkgpu_agg_kernel_ms)
     avg_kernel_ms = sum(kms) / len(kms) if kms else 0.0
@@ -371,7 +436,7 @@ def main():
                 "traffic": float(traffic) if traffic else None}
 
     cpu_baseline = None
-    if n_gpus == 1 and not args.no_cpu_baseline:
+    if args.full and n_gpus == 1 and not args.no_cpu_baseline:
         sample = min(nrows, 100_000_000)
         log(f"[bench] cpu baseline leg on {sample} rows")
         cpu_baseline = cpu_baseline_leg(cfg, sample)
