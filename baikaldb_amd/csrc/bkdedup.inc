@@ -589,6 +589,7 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
                                               int64_t row_begin,
                                               int64_t row_end) {
     if (!t || !q || q->n_group < 1) { set_err("sorted: need GROUP BY"); return nullptr; }
+    if (query_exprs_check(t, q) != 0) return nullptr;
     SortPack sp{};
     int bits_total = 0;
     bool declared = true;

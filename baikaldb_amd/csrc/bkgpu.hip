@@ -159,6 +159,105 @@ __device__ __forceinline__ bool in_list_hit(const BkConjunct& cj, int64_t v) {
  * out of line so it cannot drag the callers' hot loops with it (generic
  * shapes only; SIMPLE and the eager/dense fast paths exclude programs). */
 struct PVal { bool valid; int64_t i; double d; };
+
+/* divides_double / mod_int (operators.cpp:53-69): NULL if either operand is
+ * NULL or the divisor == 0 (-0.0 compares equal to 0, so it nulls too).
+ * DIV is DOUBLE-domain only (fn_manager.cpp:359 types divides DOUBLE; int
+ * operands arrive as their (double) view) and is the correctly rounded IEEE
+ * quotient (no fast-math). MOD is INT64-domain only: C `%`, truncated, sign
+ * of the dividend. No lane ever divides by zero: a lane whose result is
+ * NULL computes on a substituted divisor of 1, and so does a divisor of -1
+ * (x % -1 == 0 == x % 1 for every x), which DEFINES INT64_MIN % -1 — the
+ * reference's one undefined case — as 0 without a trapping idiv.
+ * Out of line on its own: the f64 divide and 64-bit remainder expansions
+ * are the costly ops of the evaluator, and eval_prog's register footprint
+ * is inherited by every generic kernel that calls it. */
+__device__ __noinline__ PVal eval_divmod(int32_t arith, bool valid,
+                                         int64_t ai, double ad,
+                                         int64_t bi, double bd) {
+    PVal o;
+    if (arith == BK_ARITH_DIV) {
+        o.valid = valid && bd != 0.0;
+        o.d = ad / (o.valid ? bd : 1.0);
+        o.i = (int64_t)o.d;
+    } else {
+        o.valid = valid && bi != 0;
+        int64_t b = (!o.valid || bi == -1) ? 1 : bi;
+        o.i = ai % b;
+        o.d = (double)o.i;
+    }
+    return o;
+}
+
+/* host-side program checker shared by every entry point that takes
+ * programs (bkgpu_filter_agg's conjunct/aggregate slots and
+ * bkgpu_table_derive_prog): operand stack within [1, BK_MAX_PROG_DEPTH],
+ * exactly one result, column refs inside the table, known opcodes, and the
+ * domain rules of bk_common.h (DIV is DOUBLE-only, MOD INT64-only, CMP arg
+ * EQ..LE). Returns nullptr when the program is sound, else what is wrong.
+ * *may_null (optional) is set when the program can yield NULL from
+ * non-NULL inputs (DIV/MOD by zero, NULLIF, a NULL literal, or an IF that
+ * may select one). */
+static const char* prog_check(const BkExprOp* p, int32_t len, int32_t ncols,
+                              bool* may_null) {
+    int sp = 0;
+    for (int32_t k = 0; k < len; k++) {
+        const BkExprOp& e = p[k];
+        int pops, pushes = 1;
+        switch (e.op) {
+            case BK_PROG_COL:
+                if (e.arg < 0 || e.arg >= ncols) return "bad column ref";
+                pops = 0;
+                break;
+            case BK_PROG_LIT_I:
+            case BK_PROG_LIT_D:
+                pops = 0;
+                break;
+            case BK_PROG_NULL:
+                if (may_null) *may_null = true;
+                pops = 0;
+                break;
+            case BK_PROG_ARITH:
+                if (e.arg < BK_ARITH_ADD || e.arg > BK_ARITH_MOD)
+                    return "bad arith op";
+                if (e.arg == BK_ARITH_DIV && e.domain != BK_DOUBLE)
+                    return "divide is DOUBLE-domain only";
+                if (e.arg == BK_ARITH_MOD && e.domain != BK_INT64)
+                    return "mod is INT64-domain only";
+                if (e.arg >= BK_ARITH_DIV && may_null) *may_null = true;
+                pops = 2;
+                break;
+            case BK_PROG_CMP:
+                if (e.arg < BK_OP_EQ || e.arg > BK_OP_LE)
+                    return "bad compare op (EQ..LE only)";
+                pops = 2;
+                break;
+            case BK_PROG_IFNULL:
+                pops = 2;
+                break;
+            case BK_PROG_NULLIF:
+                if (may_null) *may_null = true;
+                pops = 2;
+                break;
+            case BK_PROG_IF:
+                if (may_null) *may_null = true;
+                pops = 3;
+                break;
+            case BK_PROG_FN:
+            case BK_PROG_NEG:
+            case BK_PROG_ISNULL:
+                pops = 1;
+                break;
+            default:
+                return "bad opcode";
+        }
+        if (sp < pops) return "stack underflow";
+        sp += pushes - pops;
+        if (sp > BK_MAX_PROG_DEPTH) return "program too deep";
+    }
+    return sp == 1 ? nullptr : "program must leave exactly one result";
+}
+
 __device__ __noinline__ PVal eval_prog(const DevCols& cols,
                                        const BkQuerySpec& q, int32_t begin,
                                        int32_t len, int64_t r) {
@@ -196,7 +295,13 @@ __device__ __noinline__ PVal eval_prog(const DevCols& cols,
             case BK_PROG_ARITH: {
                 sp--;
                 bool v = sv[sp - 1] && sv[sp];
-                if (e.domain == BK_DOUBLE) {
+                if (e.arg >= BK_ARITH_DIV) {
+                    PVal o = eval_divmod(e.arg, v, si[sp - 1], sd[sp - 1],
+                                         si[sp], sd[sp]);
+                    si[sp - 1] = o.i;
+                    sd[sp - 1] = o.d;
+                    v = o.valid;
+                } else if (e.domain == BK_DOUBLE) {
                     double a = sd[sp - 1], b = sd[sp];
                     double o = e.arg == BK_ARITH_ADD   ? a + b
                                : e.arg == BK_ARITH_SUB ? a - b
@@ -213,11 +318,85 @@ __device__ __noinline__ PVal eval_prog(const DevCols& cols,
                 }
                 sv[sp - 1] = v;
             } break;
-            default: {                      /* BK_PROG_FN (int64 domain) */
+            case BK_PROG_FN: {              /* int64 domain */
                 int64_t o = bk_scalar_fn(e.arg, si[sp - 1]);
                 si[sp - 1] = o;
                 sd[sp - 1] = (double)o;
             } break;
+            case BK_PROG_NEG:
+                /* minus_int / minus_double (operators.cpp:31-33): int64
+                 * negation wraps (computed unsigned: -INT64_MIN ==
+                 * INT64_MIN); NULL stays NULL (sv untouched) */
+                if (e.domain == BK_DOUBLE) {
+                    sd[sp - 1] = -sd[sp - 1];
+                    si[sp - 1] = (int64_t)sd[sp - 1];
+                } else {
+                    si[sp - 1] = (int64_t)(0ull - (uint64_t)si[sp - 1]);
+                    sd[sp - 1] = (double)si[sp - 1];
+                }
+                break;
+            case BK_PROG_CMP: {
+                /* eq..le (operators.cpp:78-103): NULL if either side is,
+                 * else INT64 0/1. lt/eq/gt are tested separately so a NaN
+                 * operand compares like C (only != holds). Per-op accept
+                 * masks over {lt=1, eq=2, gt=4}, 3 bits at 3*op:
+                 * EQ 2, NE 5, GT 4, GE 6, LT 1, LE 3. */
+                sp--;
+                bool lt, eq, gt;
+                if (e.domain == BK_DOUBLE) {
+                    double a = sd[sp - 1], b = sd[sp];
+                    lt = a < b; eq = a == b; gt = a > b;
+                } else {
+                    int64_t a = si[sp - 1], b = si[sp];
+                    lt = a < b; eq = a == b; gt = a > b;
+                }
+                uint32_t m = (uint32_t)lt | ((uint32_t)eq << 1) |
+                             ((uint32_t)gt << 2);
+                uint32_t acc = (0x19D2Au >> (3 * e.arg)) & 7u;
+                bool o = e.arg == BK_OP_NE ? !eq : (acc & m) != 0;
+                sv[sp - 1] = sv[sp - 1] && sv[sp];
+                si[sp - 1] = o ? 1 : 0;
+                sd[sp - 1] = o ? 1.0 : 0.0;
+            } break;
+            case BK_PROG_IF: {
+                /* if_ (internal_functions.cpp:2383-2388): c, t, e are all
+                 * evaluated already; get_numberic<bool> of a NULL is false,
+                 * so a NULL condition selects e. The chosen operand passes
+                 * through whole — both views and its nullness. */
+                sp -= 2;
+                bool take = sv[sp - 1] && si[sp - 1] != 0;
+                si[sp - 1] = take ? si[sp] : si[sp + 1];
+                sd[sp - 1] = take ? sd[sp] : sd[sp + 1];
+                sv[sp - 1] = take ? sv[sp] : sv[sp + 1];
+            } break;
+            case BK_PROG_IFNULL: {          /* internal_functions.cpp:2390 */
+                sp--;
+                bool keep = sv[sp - 1];
+                si[sp - 1] = keep ? si[sp - 1] : si[sp];
+                sd[sp - 1] = keep ? sd[sp - 1] : sd[sp];
+                sv[sp - 1] = keep || sv[sp];
+            } break;
+            case BK_PROG_NULLIF: {
+                /* nullif (internal_functions.cpp:2410-2421): NULL iff both
+                 * non-NULL and equal in the op's compare domain, else a
+                 * (NULL a stays NULL, NULL b gives a) */
+                sp--;
+                bool eq = e.domain == BK_DOUBLE ? sd[sp - 1] == sd[sp]
+                                                : si[sp - 1] == si[sp];
+                sv[sp - 1] = sv[sp - 1] && !(sv[sp] && eq);
+            } break;
+            case BK_PROG_ISNULL: {          /* internal_functions.cpp:2397 */
+                bool nul = !sv[sp - 1];
+                si[sp - 1] = nul ? 1 : 0;
+                sd[sp - 1] = nul ? 1.0 : 0.0;
+                sv[sp - 1] = true;
+            } break;
+            default:                        /* BK_PROG_NULL (host-validated) */
+                si[sp] = 0;
+                sd[sp] = 0.0;
+                sv[sp] = false;
+                sp++;
+                break;
         }
     }
     PVal out;
@@ -2547,8 +2726,8 @@ extern "C" int bkgpu_table_derive_remap(BkgTable* t, int src_col,
  * ScalarFnCall trees per row, scalar_fn_call.cpp:194-225) into a real
  * table column, so WINDOW fn inputs, ORDER BY keys and out_cols can be
  * expressions with zero changes to the window/sort kernels. One pass over
- * the table; either-input-NULL => NULL (validity materialized only when
- * some referenced column is nullable). */
+ * the table; validity is materialized when some referenced column is
+ * nullable or the program itself can produce NULL. */
 __global__ void k_project_prog(DevCols cols, BkQuerySpec q, int64_t n,
                                int32_t out_type, void* dst, uint8_t* vout) {
     int64_t gs = (int64_t)gridDim.x * blockDim.x;
@@ -2574,40 +2753,18 @@ extern "C" int bkgpu_table_derive_prog(BkgTable* t, const BkExprOp* prog,
     if (t->ncols >= BK_MAX_COLS) { set_err("derive_prog: table full"); return -1; }
     /* validate: stack discipline + column refs (same rules as the query-
      * spec prog validator in bkgpu_filter_agg) */
+    /* non-nullable inputs can still yield NULL (x / 0, x % 0, NULLIF, a
+     * NULL literal, an IF selecting one): prog_check reports that, and the
+     * validity vector is materialized then too — COUNT(derived) must not
+     * count those rows */
     bool nullable = false;
-    {
-        int sp = 0;
-        for (int32_t k = 0; k < len; k++) {
-            const BkExprOp& e = prog[k];
-            switch (e.op) {
-                case BK_PROG_COL:
-                    if (e.arg < 0 || e.arg >= t->ncols) {
-                        set_err("derive_prog: bad column ref");
-                        return -1;
-                    }
-                    if (t->valid[e.arg]) nullable = true;
-                    /* fallthrough */
-                case BK_PROG_LIT_I:
-                case BK_PROG_LIT_D:
-                    if (++sp > BK_MAX_PROG_DEPTH) {
-                        set_err("derive_prog: program too deep");
-                        return -1;
-                    }
-                    break;
-                case BK_PROG_ARITH:
-                    if (sp < 2) { set_err("derive_prog: stack underflow"); return -1; }
-                    sp--;
-                    break;
-                case BK_PROG_FN:
-                    if (sp < 1) { set_err("derive_prog: stack underflow"); return -1; }
-                    break;
-                default:
-                    set_err("derive_prog: bad opcode");
-                    return -1;
-            }
-        }
-        if (sp != 1) { set_err("derive_prog: bad program"); return -1; }
+    if (const char* why = prog_check(prog, len, t->ncols, &nullable)) {
+        snprintf(g_err, sizeof g_err, "derive_prog: %s", why);
+        return -1;
     }
+    for (int32_t k = 0; k < len; k++)
+        if (prog[k].op == BK_PROG_COL && t->valid[prog[k].arg])
+            nullable = true;
     if (ensure_device() != 0) return -1;
     int nc = t->ncols;
     void* dcol = nullptr;
@@ -2781,6 +2938,9 @@ static int build_rec_layout(BkgTable* t, const BkQuerySpec* q, RecLayout* lay) {
     for (int a = 0; a < q->n_aggs; a++) {
         int col = q->aggs[a].col;
         if (col >= 0 && t->valid[col]) agg_meta = true;
+        /* a program's nullness is not a column property (x % 0, NULLIF, a
+         * nullable operand anywhere in the tree): always carry its bit */
+        if (q->aggs[a].prog_len > 0) agg_meta = true;
         int col2 = q->aggs[a].col2;
         if (q->aggs[a].arith && col2 >= 0 && t->valid[col2]) agg_meta = true;
     }
@@ -2873,6 +3033,47 @@ typedef void (*ScatFn)(DevCols, BkQuerySpec, RecLayout, int64_t, int64_t,
  * doubles, <= 4 conjuncts, <= 2 fn-free non-nullable group keys — the
  * sysbench/BASELINE shapes. The SIMPLE instantiations compile the unused
  * branches out of the per-row machinery. */
+/* expression validation of a query spec, run by every entry point that
+ * hands the spec to a row_passes / agg_input kernel, before any device
+ * work: every program slot passes prog_check, and the legacy single-arith
+ * slots carry ADD/SUB/MUL only — their kernels decode `arith` as
+ * "ADD ? : SUB ? : MUL", so a DIV/MOD there would silently multiply (the
+ * planner always compiles those to programs). Returns 0, or -1 with
+ * bkgpu_last_error() set. */
+static int query_exprs_check(const BkgTable* t, const BkQuerySpec* q) {
+    auto slot = [&](const char* what, int32_t arith, int32_t begin,
+                    int32_t len) -> int {
+        if (arith < 0 || arith > BK_ARITH_MUL) {
+            snprintf(g_err, sizeof g_err,
+                     "%s: arith slot takes ADD/SUB/MUL only (divide and mod "
+                     "need an expression program)", what);
+            return -1;
+        }
+        if (len == 0) return 0;
+        const char* why = nullptr;
+        if (begin < 0 || len < 0 || q->n_prog < 0 ||
+            q->n_prog > BK_MAX_PROG_POOL || begin > q->n_prog - len)
+            why = "program outside the pool";
+        else
+            why = prog_check(q->prog + begin, len, t->ncols, nullptr);
+        if (why) {
+            snprintf(g_err, sizeof g_err, "bad %s expression program: %s",
+                     what, why);
+            return -1;
+        }
+        return 0;
+    };
+    for (int32_t j = 0; j < q->n_conjuncts && j < BK_MAX_CONJUNCTS; j++)
+        if (slot("conjunct", q->conjuncts[j].arith,
+                 q->conjuncts[j].prog_begin, q->conjuncts[j].prog_len) != 0)
+            return -1;
+    for (int32_t a = 0; a < q->n_aggs && a < BK_MAX_AGGS; a++)
+        if (slot("aggregate", q->aggs[a].arith, q->aggs[a].prog_begin,
+                 q->aggs[a].prog_len) != 0)
+            return -1;
+    return 0;
+}
+
 static bool query_simple(const BkgTable* t, const BkQuerySpec* q) {
     if (q->n_conjuncts > 4 || q->n_group > 2) return false;
     for (int32_t j = 0; j < q->n_conjuncts; j++) {
@@ -3331,50 +3532,8 @@ extern "C" BkgAggOut* bkgpu_filter_agg(BkgTable* t, const BkQuerySpec* q,
                 set_err("or_group out of range (0..31)");
                 return nullptr;
             }
-    if (q) {
-        /* postfix-program validation: indices in the pool, operand stack
-         * within [1, BK_MAX_PROG_DEPTH], exactly one result */
-        auto bad_prog = [&](int32_t begin, int32_t len) -> bool {
-            if (len == 0) return false;
-            if (begin < 0 || len < 0 || q->n_prog > BK_MAX_PROG_POOL ||
-                begin + len > q->n_prog)
-                return true;
-            int sp = 0;
-            for (int32_t k = 0; k < len; k++) {
-                const BkExprOp& e = q->prog[begin + k];
-                switch (e.op) {
-                    case BK_PROG_COL:
-                        if (e.arg < 0 || e.arg >= t->ncols) return true;
-                        /* fallthrough */
-                    case BK_PROG_LIT_I:
-                    case BK_PROG_LIT_D:
-                        if (++sp > BK_MAX_PROG_DEPTH) return true;
-                        break;
-                    case BK_PROG_ARITH:
-                        if (sp < 2) return true;
-                        sp--;
-                        break;
-                    case BK_PROG_FN:
-                        if (sp < 1) return true;
-                        break;
-                    default:
-                        return true;
-                }
-            }
-            return sp != 1;
-        };
-        for (int32_t j = 0; j < q->n_conjuncts; j++)
-            if (bad_prog(q->conjuncts[j].prog_begin,
-                         q->conjuncts[j].prog_len)) {
-                set_err("bad conjunct expression program");
-                return nullptr;
-            }
-        for (int32_t a = 0; a < q->n_aggs; a++)
-            if (bad_prog(q->aggs[a].prog_begin, q->aggs[a].prog_len)) {
-                set_err("bad aggregate expression program");
-                return nullptr;
-            }
-    }
+    /* postfix programs + legacy arith slots (query_exprs_check) */
+    if (q && t && query_exprs_check(t, q) != 0) return nullptr;
     if (ensure_device() != 0) return nullptr;
     double t_start = debug_timing() ? now_ms() : 0;
     double t_alloc = 0, t_pipe = 0;
@@ -4058,6 +4217,7 @@ k_filter_collect(DevCols cols, BkQuerySpec q, int64_t row_begin, int64_t row_end
 extern "C" int64_t bkgpu_filter_collect(BkgTable* t, const BkQuerySpec* q,
                                         int64_t row_begin, int64_t row_end,
                                         int64_t limit, int64_t* out_rowids_host) {
+    if (t && q && query_exprs_check(t, q) != 0) return -1;
     if (ensure_device() != 0) return -1;
     if (limit <= 0) return 0;
     int64_t* d_ids = nullptr;

@@ -487,6 +487,7 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
                                    const BkOrderSpec* order, int norder,
                                    int64_t row_begin, int64_t row_end,
                                    int64_t limit, int64_t* out_rows) {
+    if (t && q && query_exprs_check(t, q) != 0) return -1;
     if (ensure_device() != 0) return -1;
     if (norder < 1 || norder > TOPK_MAX_ORDER) { set_err("bad norder"); return -1; }
     if (limit <= 0) return 0;

@@ -50,6 +50,47 @@ class BkExprOp(C.Structure):
 
 BK_MAX_PROG_POOL = 32
 PROG_COL, PROG_LIT_I, PROG_LIT_D, PROG_ARITH, PROG_FN = 0, 1, 2, 3, 4
+(PROG_NEG, PROG_CMP, PROG_IF, PROG_IFNULL, PROG_NULLIF, PROG_ISNULL,
+ PROG_NULL) = 5, 6, 7, 8, 9, 10, 11
+ARITH_DIV, ARITH_MOD = 4, 5
+_CMPS = {"eq": OP_EQ, "ne": OP_NE, "gt": OP_GT, "ge": OP_GE, "lt": OP_LT,
+         "le": OP_LE}
+# tags that always compile to a postfix program (never the legacy
+# single-arith / single-fn slots of BkConjunct / BkAggSpec)
+_PROG_ONLY = frozenset(_CMPS) | {"div", "mod", "neg", "if", "ifnull",
+                                 "nullif", "isnull", "null", "case",
+                                 "case_expr"}
+
+
+def _merged(d1, d2):
+    return TYPE_DOUBLE if TYPE_DOUBLE in (d1, d2) else TYPE_INT64
+
+
+def _compile_if_tail(cond_then, else_, col_types, pool, x=None):
+    """Lower the WHEN list of a CASE to nested IFs (postfix: c t <rest> IF).
+    With x (a case_expr subject) every WHEN value w becomes the condition
+    x = w. Returns the merged branch domain."""
+    if not cond_then:
+        if else_ is None:               # a missing ELSE is a NULL literal
+            pool.append(dict(op=PROG_NULL))
+            return TYPE_INT64
+        return compile_expr(else_, col_types, pool)
+    (c, t), rest = cond_then[0], cond_then[1:]
+    _compile_cond(("eq", x, c) if x is not None else c, col_types, pool)
+    dt = compile_expr(t, col_types, pool)
+    de = _compile_if_tail(rest, else_, col_types, pool, x)
+    pool.append(dict(op=PROG_IF, domain=_merged(dt, de)))
+    return _merged(dt, de)
+
+
+def _compile_cond(c, col_types, pool):
+    """Compile an IF/CASE condition to an INT64 truth value. The reference
+    tests it with get_numberic<bool> (internal_functions.cpp:2355,2387), so
+    a DOUBLE 0.5 is true; the kernel tests the stack's int view, where 0.5
+    is 0 — a DOUBLE-typed condition therefore gets `ne 0.0` appended."""
+    if compile_expr(c, col_types, pool) == TYPE_DOUBLE:
+        pool.append(dict(op=PROG_LIT_D, lit_d=0.0))
+        pool.append(dict(op=PROG_CMP, arg=OP_NE, domain=TYPE_DOUBLE))
 
 
 def compile_expr(e, col_types, pool):
@@ -62,7 +103,12 @@ def compile_expr(e, col_types, pool):
 
     Operands: int = column index; float = double literal;
     ("liti", v) / ("litf", v) explicit literals;
-    ("add"|"sub"|"mul", a, b); scalar fns ("year"|..., a)."""
+    ("add"|"sub"|"mul", a, b); scalar fns ("year"|..., a);
+    ("div", a, b) (always DOUBLE), ("mod", a, b) (INT64 only), ("neg", a);
+    ("eq"|"ne"|"gt"|"ge"|"lt"|"le", a, b) -> INT64 0/1;
+    ("if", c, t, e), ("ifnull", a, b), ("nullif", a, b), ("isnull", a),
+    ("null",); ("case", [(c, t), ...], else_or_None) and
+    ("case_expr", x, [(w, t), ...], else_or_None), lowered to nested IFs."""
     if isinstance(e, bool):
         raise ValueError("bool is not an expression operand")
     if isinstance(e, int):
@@ -88,6 +134,74 @@ def compile_expr(e, col_types, pool):
         compile_expr(e[1], col_types, pool)
         pool.append(dict(op=PROG_FN, arg=_FNS[tag]))
         return TYPE_INT64
+    if tag == "div":
+        # divides is typed DOUBLE by the planner (fn_manager.cpp:359): the
+        # only divide is the f64 one, int operands use their double view
+        compile_expr(e[1], col_types, pool)
+        compile_expr(e[2], col_types, pool)
+        pool.append(dict(op=PROG_ARITH, arg=ARITH_DIV, domain=TYPE_DOUBLE))
+        return TYPE_DOUBLE
+    if tag == "mod":
+        # mod is registered for integers only (operators.cpp:68-69)
+        d1 = compile_expr(e[1], col_types, pool)
+        d2 = compile_expr(e[2], col_types, pool)
+        if TYPE_DOUBLE in (d1, d2):
+            raise ValueError("mod needs INT64 operands (no DOUBLE mod)")
+        pool.append(dict(op=PROG_ARITH, arg=ARITH_MOD, domain=TYPE_INT64))
+        return TYPE_INT64
+    if tag == "neg":
+        dom = compile_expr(e[1], col_types, pool)
+        pool.append(dict(op=PROG_NEG, domain=dom))
+        return dom
+    if tag in _CMPS:
+        # compare domain: DOUBLE iff either side is (operators.cpp:78-103);
+        # the result is an INT64 0/1 truth value
+        d1 = compile_expr(e[1], col_types, pool)
+        d2 = compile_expr(e[2], col_types, pool)
+        pool.append(dict(op=PROG_CMP, arg=_CMPS[tag], domain=_merged(d1, d2)))
+        return TYPE_INT64
+    if tag == "if":
+        # if_(c, t, e), internal_functions.cpp:2383-2388. All three children
+        # are evaluated before the call (ScalarFnCall::get_value), so the
+        # postfix form is exact. Result domain: DOUBLE iff either branch is
+        # (has_merged_type).
+        _compile_cond(e[1], col_types, pool)
+        dt = compile_expr(e[2], col_types, pool)
+        de = compile_expr(e[3], col_types, pool)
+        pool.append(dict(op=PROG_IF, domain=_merged(dt, de)))
+        return _merged(dt, de)
+    if tag == "ifnull":
+        d1 = compile_expr(e[1], col_types, pool)
+        d2 = compile_expr(e[2], col_types, pool)
+        pool.append(dict(op=PROG_IFNULL, domain=_merged(d1, d2)))
+        return _merged(d1, d2)
+    if tag == "nullif":
+        # NULL iff both non-NULL and equal in the compare domain, else a —
+        # the result keeps a's own domain
+        d1 = compile_expr(e[1], col_types, pool)
+        d2 = compile_expr(e[2], col_types, pool)
+        pool.append(dict(op=PROG_NULLIF, domain=_merged(d1, d2)))
+        return d1
+    if tag == "isnull":
+        compile_expr(e[1], col_types, pool)
+        pool.append(dict(op=PROG_ISNULL))
+        return TYPE_INT64
+    if tag == "null":
+        pool.append(dict(op=PROG_NULL))
+        return TYPE_INT64
+    if tag == "case":
+        # case_when(c1,t1,...[,else]) (internal_functions.cpp:2351-2365) ==
+        # if(c1, t1, if(c2, t2, ... else)): every argument is evaluated
+        # eagerly and side-effect free, so the nesting is exact
+        return _compile_if_tail(list(e[1]), e[2] if len(e) > 2 else None,
+                                col_types, pool)
+    if tag == "case_expr":
+        # case_expr_when(x,w1,t1,...[,else]) (internal_functions.cpp:
+        # 2367-2381) with each match lowered to `x eq w`. Single divergence:
+        # the reference's compare_diff_type calls NULL x vs NULL w equal
+        # (expr_value.h:938-939); the eq lowering yields NULL = no match.
+        return _compile_if_tail(list(e[2]), e[3] if len(e) > 3 else None,
+                                col_types, pool, x=e[1])
     raise ValueError(f"bad expression node: {e!r}")
 
 
@@ -96,7 +210,7 @@ def expr_is_deep(e):
     beyond the legacy one-arith / one-fn shapes with plain column refs)."""
     if not isinstance(e, tuple):
         return False
-    if e[0] in ("liti", "litf"):
+    if e[0] in ("liti", "litf") or e[0] in _PROG_ONLY:
         return True
     return any(isinstance(x, (tuple, float)) for x in e[1:])
 

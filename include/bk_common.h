@@ -181,6 +181,16 @@ typedef enum BkArith {
     BK_ARITH_ADD = 1,
     BK_ARITH_SUB = 2,
     BK_ARITH_MUL = 3,
+    /* divides / mod (operators.cpp:53-69). PROGRAM ops only: the legacy
+     * single-arith slots (BkConjunct.arith, BkAggSpec.arith) accept
+     * ADD/SUB/MUL and the validators reject anything above BK_ARITH_MUL.
+     *   DIV: DOUBLE domain only (the planner types divides DOUBLE,
+     *        fn_manager.cpp:359); NULL when the divisor == 0 (-0.0 too).
+     *   MOD: INT64 domain only (no double mod is registered); NULL when
+     *        the divisor is 0; C `%` otherwise (sign of the dividend).
+     *        INT64_MIN % -1 — undefined in the reference — is DEFINED 0. */
+    BK_ARITH_DIV = 4,
+    BK_ARITH_MOD = 5,
 } BkArith;
 
 /* One aggregate call (reference: src/expr/agg_fn_call.cpp:496-555 update,
@@ -215,12 +225,30 @@ typedef enum BkProgOp {
     BK_PROG_LIT_D = 2,   /* push double literal */
     BK_PROG_ARITH = 3,   /* pop b, a -> push a OP b (arg = BkArith) */
     BK_PROG_FN    = 4,   /* pop a -> push fn(a) (arg = BkScalarFn, int64) */
+    /* unary minus (operators.cpp:18-33): INT64 wraps (-INT64_MIN ==
+     * INT64_MIN), DOUBLE flips the sign; NULL stays NULL */
+    BK_PROG_NEG    = 5,  /* pop a -> push -a (domain) */
+    /* eq/ne/gt/ge/lt/le inside a program (operators.cpp:78-103): NULL if
+     * either side is NULL, else INT64 0/1; compares in `domain` */
+    BK_PROG_CMP    = 6,  /* pop b, a -> push a <cmp> b (arg = BkCmpOp EQ..LE) */
+    /* the conditional family (internal_functions.cpp:2351-2421). The
+     * reference evaluates every child before calling the fn
+     * (ScalarFnCall::get_value), so popping already-evaluated operands is
+     * exact. The chosen operand passes through whole (value + nullness). */
+    BK_PROG_IF     = 7,  /* pop e, t, c -> push (c non-NULL and != 0) ? t : e
+                            (c is an INT64 truth value) */
+    BK_PROG_IFNULL = 8,  /* pop b, a -> push a non-NULL ? a : b */
+    BK_PROG_NULLIF = 9,  /* pop b, a -> push NULL iff both non-NULL and equal
+                            in `domain`, else a */
+    BK_PROG_ISNULL = 10, /* pop a -> push INT64 1/0 (never NULL) */
+    BK_PROG_NULL   = 11, /* push a NULL */
 } BkProgOp;
 
 typedef struct BkExprOp {
     int32_t op;        /* BkProgOp */
     int32_t arg;
-    int32_t domain;    /* BK_INT64 or BK_DOUBLE (ARITH compute domain) */
+    int32_t domain;    /* BK_INT64 or BK_DOUBLE: ARITH/NEG compute domain,
+                          CMP/NULLIF compare domain */
     int32_t _pad;
     int64_t lit_i;
     double  lit_d;
