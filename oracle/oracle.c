@@ -165,7 +165,24 @@ static OrcPVal orc_eval_prog(const OrcCol* cols, const BkQuerySpec* q,
             case BK_PROG_ARITH: {
                 sp--;
                 int v = sv[sp - 1] && sv[sp];
-                if (e->domain == BK_DOUBLE) {
+                if (e->arg == BK_ARITH_DIV) {
+                    /* divides_double (operators.cpp:53-60): NULL when the
+                     * divisor is 0 (-0.0 too); DOUBLE domain only */
+                    double a = sd[sp - 1], b = sd[sp];
+                    v = v && b != 0.0;
+                    double o = v ? a / b : 0.0;
+                    sd[sp - 1] = o;
+                    si[sp - 1] = v ? (int64_t)o : 0;
+                } else if (e->arg == BK_ARITH_MOD) {
+                    /* mod_int (operators.cpp:62-69): NULL when the divisor
+                     * is 0; C %, sign of the dividend. INT64_MIN % -1 is
+                     * defined 0 (bk_common.h) */
+                    int64_t a = si[sp - 1], b = si[sp];
+                    v = v && b != 0;
+                    int64_t o = (!v || b == -1) ? 0 : a % b;
+                    si[sp - 1] = o;
+                    sd[sp - 1] = (double)o;
+                } else if (e->domain == BK_DOUBLE) {
                     double a = sd[sp - 1], b = sd[sp];
                     double o = e->arg == BK_ARITH_ADD   ? a + b
                                : e->arg == BK_ARITH_SUB ? a - b
@@ -182,9 +199,91 @@ static OrcPVal orc_eval_prog(const OrcCol* cols, const BkQuerySpec* q,
                 }
                 sv[sp - 1] = v;
             } break;
-            default:                           /* BK_PROG_FN */
+            case BK_PROG_FN:
                 si[sp - 1] = bk_scalar_fn(e->arg, si[sp - 1]);
                 sd[sp - 1] = (double)si[sp - 1];
+                break;
+            case BK_PROG_NEG:
+                /* minus_int wraps (-INT64_MIN == INT64_MIN), minus_double
+                 * flips the sign (operators.cpp:18-33); NULL stays NULL */
+                if (e->domain == BK_DOUBLE) {
+                    sd[sp - 1] = -sd[sp - 1];
+                    si[sp - 1] = (int64_t)sd[sp - 1];
+                } else {
+                    si[sp - 1] = (int64_t)(0ull - (uint64_t)si[sp - 1]);
+                    sd[sp - 1] = (double)si[sp - 1];
+                }
+                break;
+            case BK_PROG_CMP: {
+                /* eq..le (operators.cpp:78-103): NULL if either side is,
+                 * else INT64 0/1, compared in the op's domain */
+                sp--;
+                int o;
+                if (e->domain == BK_DOUBLE) {
+                    double a = sd[sp - 1], b = sd[sp];
+                    o = e->arg == BK_OP_EQ   ? a == b
+                        : e->arg == BK_OP_NE ? a != b
+                        : e->arg == BK_OP_GT ? a > b
+                        : e->arg == BK_OP_GE ? a >= b
+                        : e->arg == BK_OP_LT ? a < b
+                                             : a <= b;
+                } else {
+                    int64_t a = si[sp - 1], b = si[sp];
+                    o = e->arg == BK_OP_EQ   ? a == b
+                        : e->arg == BK_OP_NE ? a != b
+                        : e->arg == BK_OP_GT ? a > b
+                        : e->arg == BK_OP_GE ? a >= b
+                        : e->arg == BK_OP_LT ? a < b
+                                             : a <= b;
+                }
+                sv[sp - 1] = sv[sp - 1] && sv[sp];
+                si[sp - 1] = o;
+                sd[sp - 1] = (double)o;
+            } break;
+            case BK_PROG_IF: {
+                /* if_(c, t, e) (internal_functions.cpp:2383-2388): a NULL or
+                 * zero condition selects e; the chosen operand passes
+                 * through whole, nullness included */
+                sp -= 2;
+                int pick = (sv[sp - 1] && si[sp - 1] != 0) ? sp : sp + 1;
+                si[sp - 1] = si[pick];
+                sd[sp - 1] = sd[pick];
+                sv[sp - 1] = sv[pick];
+            } break;
+            case BK_PROG_IFNULL:               /* a non-NULL ? a : b */
+                sp--;
+                if (!sv[sp - 1]) {
+                    si[sp - 1] = si[sp];
+                    sd[sp - 1] = sd[sp];
+                    sv[sp - 1] = sv[sp];
+                }
+                break;
+            case BK_PROG_NULLIF: {
+                /* NULL iff both non-NULL and equal in the op's domain, else
+                 * a (internal_functions.cpp:2410-2421) */
+                sp--;
+                if (sv[sp - 1] && sv[sp]) {
+                    int eq = e->domain == BK_DOUBLE ? sd[sp - 1] == sd[sp]
+                                                    : si[sp - 1] == si[sp];
+                    if (eq) sv[sp - 1] = 0;
+                }
+            } break;
+            case BK_PROG_ISNULL: {
+                int nul = !sv[sp - 1];
+                si[sp - 1] = nul;
+                sd[sp - 1] = (double)nul;
+                sv[sp - 1] = 1;
+            } break;
+            case BK_PROG_NULL:
+                si[sp] = 0;
+                sd[sp] = 0.0;
+                sv[sp] = 0;
+                sp++;
+                break;
+            default:    /* unknown opcode: poison the row, never guess */
+                si[0] = 0; sd[0] = 0.0; sv[0] = 0;
+                k = len;
+                sp = 1;
                 break;
         }
     }

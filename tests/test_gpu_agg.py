@@ -42,8 +42,12 @@ def orc():
 
 
 def run_both(eng, orc, spec_rows, n, conjuncts, group, aggs, nthreads=4,
-             expected_groups=1 << 14, seed=SEED, group_bits=(), group_base=()):
-    """conjuncts: (col, op_sym, lit); aggs: (name, col)."""
+             expected_groups=1 << 14, seed=SEED, group_bits=(), group_base=(),
+             info=None, row_begin=0, row_end=None):
+    """conjuncts: (col, op_sym, lit); aggs: (name, col).
+    info: optional dict; receives info["breakdown"] = the engine's kernel
+    breakdown names (the route taken). row_begin/row_end restrict both the
+    engine and the oracle to that row range (default: the whole table)."""
     t = eng.create_table(spec_rows, n)
     try:
         eng.generate(t, seed)
@@ -51,8 +55,11 @@ def run_both(eng, orc, spec_rows, n, conjuncts, group, aggs, nthreads=4,
         plan = QueryPlan(t.col_types, conjuncts=conjuncts, group=group,
                          aggs=aggs, group_bits=group_bits,
                          group_base=group_base)
-        res = eng.filter_agg(t, plan, expected_groups=expected_groups)
+        res = eng.filter_agg(t, plan, row_begin=row_begin, row_end=row_end,
+                             expected_groups=expected_groups)
         try:
+            if info is not None:
+                info["breakdown"] = list(res.breakdown())
             got = res.fetch(sorted=True)
         finally:
             res.free()
@@ -106,7 +113,7 @@ def run_both(eng, orc, spec_rows, n, conjuncts, group, aggs, nthreads=4,
     q = make_query(oconj, ogroup, oaggs, col_types,
                    group_bits=group_bits, group_base=group_base)
     exp = orc.filter_agg(cols, valids, col_types, q, nthreads=nthreads,
-                         dict_seed=seed)
+                         dict_seed=seed, row_begin=row_begin, row_end=row_end)
     return got, exp
 
 

