@@ -1967,8 +1967,21 @@ __global__ void k_merge_blob(BkQuerySpec q, const uint32_t* flags, const uint64_
     const int stride = SLOT_HDR + 2 * q.n_aggs;
     int64_t gs = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gs) {
-        uint64_t* s = gtable_claim(gtable, gmask, stride, flags[i], k0[i], k1[i],
-                                   fill, fill_cap, err);
+        uint64_t* s;
+        if (q.n_group == 0) {
+            /* no GROUP BY: the single group lives in slot 0 of EVERY table
+             * and nowhere else (filter_agg and rollup pre-claim it on the
+             * host) — never placed by hash. A fresh bkgpu_agg_empty table
+             * claims it here on its first merge; flag/k0/k1 are all zero,
+             * as agg_alloc's memset left them, so state 0 -> 2 publishes
+             * the whole header in one step. */
+            s = gtable;
+            if (atomicCAS((uint32_t*)s, 0u, 2u) == 0u)
+                atomicAdd((unsigned long long*)fill, 1ull);
+        } else {
+            s = gtable_claim(gtable, gmask, stride, flags[i], k0[i], k1[i],
+                             fill, fill_cap, err);
+        }
         if (!s) return;
         agg_merge_slot<false>(s, states + i * (uint64_t)(2 * q.n_aggs), q);
     }
@@ -2882,6 +2895,8 @@ static int agg_compact(BkgAggOut* o) {
     uint64_t ctr_host[3];
     HIP_CHECK(hipMemcpy(ctr_host, o->ctrs, 24, hipMemcpyDeviceToHost));
     int64_t fill = (int64_t)ctr_host[0];
+    /* no GROUP BY: slot 0 is the only slot any producer or merge ever
+     * claims (see k_merge_blob), so one group is exact, not a truncation */
     if (o->q.n_group == 0) fill = 1;
     cap = fill > 0 ? fill : 1;
     if (o->blob) { pool_free(o->blob); o->blob = nullptr; }
@@ -3699,7 +3714,10 @@ extern "C" BkgAggOut* bkgpu_filter_agg(BkgTable* t, const BkQuerySpec* q,
         agg_release_table(o);
         nslots *= 4;
         if (attempt == 7) {
-            set_err("hash table overflow after retries");
+            /* err 2 = fill crossed 7/8 of the table, 1 = probe limit */
+            snprintf(g_err, sizeof g_err, "hash table overflow after retries "
+                     "(err %u at %lld slots)", err_host,
+                     (long long)(nslots / 4));
             bkgpu_agg_free(o);
             return nullptr;
         }
@@ -4022,12 +4040,13 @@ extern "C" int bkgpu_agg_export_part(const BkgAggOut* o_, int nparts,
                                      int part, void* dst,
                                      int64_t part_groups) {
     BkgAggOut* o = const_cast<BkgAggOut*>(o_);
-    if (nparts < 1 || part < 0 || part >= nparts) {
+    if (nparts < 1 || nparts > 16384 || part < 0 || part >= nparts ||
+        part_groups < 0) {
         set_err("bad part");
         return -1;
     }
     if (agg_compact(o) != 0) return -1;
-    if (part_groups <= 0) return 0;
+    if (o->ngroups <= 0) return 0;
     uint64_t* cursor = nullptr;
     HIP_CHECK(pool_alloc((void**)&cursor, 8));
     HIP_CHECK(hipMemset(cursor, 0, 8));
@@ -4044,9 +4063,22 @@ extern "C" int bkgpu_agg_export_part(const BkgAggOut* o_, int nparts,
                        (const uint64_t*)(b + c * 20), o->ngroups,
                        o->q.n_aggs, nparts, part, cursor, of, ok0, ok1, ost,
                        (uint64_t)part_groups);
-    HIP_CHECK(hipGetLastError());
-    HIP_CHECK(hipDeviceSynchronize());
+    hipError_t lerr = hipGetLastError();
+    /* the kernel drops groups past part_groups (its writes stay in bounds);
+     * the cursor counts every group of the part, so a stale or undersized
+     * part_groups is an error here instead of a silently short blob */
+    uint64_t written = 0;
+    if (lerr == hipSuccess)
+        lerr = hipMemcpy(&written, cursor, 8, hipMemcpyDeviceToHost);
     pool_free(cursor);
+    HIP_CHECK(lerr);
+    if (written > (uint64_t)part_groups) {
+        snprintf(g_err, sizeof g_err,
+                 "export_part: part %d of %d holds %llu groups, part_groups "
+                 "%lld is too small", part, nparts,
+                 (unsigned long long)written, (long long)part_groups);
+        return -1;
+    }
     return 0;
 }
 

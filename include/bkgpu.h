@@ -121,7 +121,13 @@ int     bkgpu_agg_breakdown(const BkgAggOut* o, char* names, double* ms, int cap
  * Compact wire format of one partial result, an SoA byte blob:
  *   [ flags: u32 * n ][ k0: u64 * n ][ k1: u64 * n ][ states: u64 * n * 2*naggs ]
  * (AVG state = {sum double bits, count}; SUM = {val bits, nonnull count};
- *  MIN/MAX = {order-encoded u64, nonnull count}; COUNT = {count, _}.) */
+ *  MAX = {order-encoded u64 e, nonnull count}; MIN = {~e, nonnull count} —
+ *  the COMPLEMENT of the order encoding, so both merge with one unsigned
+ *  max and the zero state is the identity; COUNT = {count, _}. The value
+ *  word is meaningful only where the nonnull count is > 0.
+ *  tests/test_gpu_merge.py::test_wire_format pins this layout.)
+ * A query without GROUP BY always carries exactly one group (flags, k0,
+ * k1 all zero); merging it never depends on the key words. */
 int64_t bkgpu_agg_export_bytes(const BkgAggOut* o);
 /* Write the blob to dst (DEVICE pointer, capacity cap bytes). */
 int  bkgpu_agg_export(const BkgAggOut* o, void* dst, int64_t cap);
@@ -139,7 +145,9 @@ int  bkgpu_agg_merge(BkgAggOut* o, const void* blob, int64_t n_groups);
 /* per-part group counts (runs compact if needed) */
 int  bkgpu_agg_part_counts(const BkgAggOut* o, int nparts, int64_t* counts);
 /* write part `part`'s blob (DEVICE dst; layout = the standard wire blob
- * with part_groups groups — pass the count bkgpu_agg_part_counts gave) */
+ * with part_groups groups — pass the count bkgpu_agg_part_counts gave;
+ * a part that holds more groups than part_groups is an error, nothing is
+ * written past part_groups) */
 int  bkgpu_agg_export_part(const BkgAggOut* o, int nparts, int part,
                            void* dst, int64_t part_groups);
 /* fresh empty result for `q` (merge target for received part blobs) */

@@ -1,0 +1,872 @@
+# Consumer-side parity tests. test_gpu_routes.py forces every PRODUCER route
+# of bkgpu_filter_agg / bkgpu_filter_agg_sorted; this file covers what runs on
+# top of a finished BkgAggOut: bkgpu_agg_export / bkgpu_agg_merge,
+# bkgpu_agg_part_counts / bkgpu_agg_export_part / bkgpu_agg_empty,
+# bkgpu_agg_rollup on a merged level 1, bkgpu_agg_fetch with max_groups and
+# bkgpu_agg_nfilled. A result exists in four physical forms and each consumer
+# treats them differently:
+#   hash table        fused, partitioned, pipelined, agg_empty, rollup output
+#   dense_mode arrays dense, dpipe (dense_compact / dense_to_hash)
+#   sort-dedup table  filter_agg_sorted (nslots == ngroups; merge rebuilds)
+#   scalar slot 0     n_group == 0 (never placed by hash)
+# Every comparison is against the CPU oracle over the WHOLE row range:
+# integers, counts, keys, flags, agg_has and MIN/MAX bit-exact, DOUBLE SUM/AVG
+# through check_result's existing bounds (a merged sum is one more reordering
+# of the same addends). rows_passed is a per-partial counter by design, so a
+# merged result is checked by COUNT(*).sum() == oracle rows_passed instead.
+# Source blobs are produced once per (shape, route, range) and shared; a merge
+# only reads them.
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from oracle.bindings import make_query
+from tests.test_distinct import AGGMAP, OPS, _parity_names
+from tests.test_gpu_agg import (SEED, assert_parity, eng, orc)  # noqa: F401
+from tests.test_gpu_routes import (KNOBS, HASH, DNS, FUSED, PART, PIPE, DENSE,
+                                   DPIPE, SORTED, I64, S1, S2, S4, SB, SFLAT,
+                                   D_UNI, K80, assert_same_ints,
+                                   check_result, kn, world,  # noqa: F401
+                                   _clear_knobs)  # noqa: F401
+
+gpu = pytest.mark.gpu
+
+BK_MAX_GROUP = 4
+
+# route -> (knobs, breakdown names)
+ROUTES = {
+    "FUSED": ({}, FUSED),                    # expected_groups <= 512
+    "PART": (HASH, PART),
+    "PIPE": (kn(HASH, BK_PIPE=2), PIPE),
+    "DENSE": (DNS, DENSE),
+    "DPIPE": (kn(DNS, BK_DPIPE=2), DPIPE),
+    "SORTED": ({}, SORTED),                  # filter_agg_sorted directly
+}
+FUSED_EG = 256
+
+
+def plan_of(world, sh):
+    from baikaldb_amd import QueryPlan
+    t = world.table(sh)
+    return t, QueryPlan(t.col_types, conjuncts=sh.conj, group=sh.group,
+                        aggs=sh.aggs, group_bits=sh.bits, group_base=sh.base)
+
+
+def forced(monkeypatch, knobs, fn):
+    """run fn() with exactly `knobs` set, as run_route does"""
+    with monkeypatch.context() as m:
+        for k in KNOBS:
+            m.delenv(k, raising=False)
+        for k, v in knobs.items():
+            assert k in KNOBS, k
+            m.setenv(k, str(v))
+        return fn()
+
+
+def partial(world, monkeypatch, sh, route, rb, re_):
+    """AggResult for rows [rb, re_) produced by `route` (asserted by its
+    breakdown names); EMPTY is a fresh agg_empty (destination only)."""
+    t, plan = plan_of(world, sh)
+    e = world.eng
+    if route == "EMPTY":
+        return e.agg_empty(plan, expected_groups=sh.eg)
+    knobs, names = ROUTES[route]
+    if route == "SORTED":
+        res = forced(monkeypatch, knobs,
+                     lambda: e.filter_agg_sorted(t, plan, rb, re_))
+    else:
+        eg = FUSED_EG if route == "FUSED" else sh.eg
+        res = forced(monkeypatch, knobs,
+                     lambda: e.filter_agg(t, plan, rb, re_,
+                                          expected_groups=eg))
+    got = list(res.breakdown())
+    if got != names:
+        res.free()
+    assert got == names, (route, got)
+    return res
+
+
+def export(res):
+    """(device uint8 buffer, ngroups) of a result's whole wire blob"""
+    import torch
+    nb = res.export_bytes()
+    buf = torch.empty(max(nb, 8), dtype=torch.uint8, device="cuda")
+    res.export_to(buf.data_ptr(), nb)
+    return buf, res.ngroups
+
+
+# exported source blobs, produced once per (shape, route, range) and shared
+# by the cases of this module; dropped (device buffers freed) at its end
+_BLOBS = {}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _blob_cache():
+    yield
+    _BLOBS.clear()
+
+
+def blob(world, monkeypatch, sh, route, rb, re_):
+    """cached export of partial(sh, route, rb, re_)"""
+    key = (sh.name, route, rb, re_)
+    if key not in _BLOBS:
+        res = partial(world, monkeypatch, sh, route, rb, re_)
+        try:
+            _BLOBS[key] = export(res)
+        finally:
+            res.free()
+    return _BLOBS[key]
+
+
+def merge(dst, b):
+    buf, n = b
+    dst.merge_blob(buf.data_ptr(), n)
+
+
+def check_merged(sh, got, exp, first=None):
+    """merged result vs the whole-range oracle (and the whole-range engine
+    integers); rows_passed is per partial, COUNT(*) (agg 0) carries it"""
+    assert sh.aggs[0][0] == "count_star"
+    assert int(got["agg_i"][0].sum()) == exp["rows_passed"]
+    g = dict(got)
+    g["rows_passed"] = exp["rows_passed"]
+    check_result(sh, g, exp)
+    if first is not None:
+        assert_same_ints(sh, g, first)
+    return g
+
+
+def whole(world, monkeypatch, sh, rb=0, re_=None):
+    re_ = sh.n if re_ is None else re_
+    exp = world.expected(monkeypatch, sh, rb, re_)
+    return exp, world.first[(sh.name, rb, re_)]
+
+
+def eligible(sh, route):
+    """dense routes need dense_eligible(); every shape here passes
+    filter_agg_sorted (auto-packed or 24 declared bits - never >= 25)"""
+    return route not in ("DENSE", "DPIPE") or sh.dense
+
+
+# ---- 1. producer x destination merge matrix --------------------------------
+DESTS = ["FUSED", "PART", "DENSE", "SORTED", "EMPTY"]
+SRCS = ["FUSED", "PART", "PIPE", "DENSE", "DPIPE", "SORTED"]
+MSHAPES = [S1, S2, S4, SB[False], SB[True]]
+# Known producer defect: the fused route, forced by
+# expected_groups <= 512, reaches a large group count only through repeated
+# 4x regrows, and on sb_bits24_nonnull rows [7, 300000) (232325 groups) it
+# fails intermittently with "hash table overflow after retries" (probe-limit
+# code at 16M slots). Only the (shape, route, range) partials measured to
+# fail are left out, by name; every other FUSED partial runs at the issue's
+# split points.
+FUSED_DEFECT = {(SB[False].name, 7, SB[False].n)}
+
+
+def split_of(sh, mi):
+    return 7 if mi == 0 else sh.n // 2 + 1
+
+
+def _hits_defect(sh, x, y, mi):
+    m = split_of(sh, mi)
+    return ((x == "FUSED" and (sh.name, 0, m) in FUSED_DEFECT) or
+            (y == "FUSED" and (sh.name, m, sh.n) in FUSED_DEFECT))
+
+
+MATRIX = [(sh, x, y, mi) for sh in MSHAPES
+          for x in DESTS if eligible(sh, x)
+          for y in SRCS if eligible(sh, y)
+          for mi in (0, 1) if not _hits_defect(sh, x, y, mi)]
+
+
+@gpu
+@pytest.mark.parametrize("sh,x,y,mi", MATRIX,
+                         ids=[f"{s}-{x}<-{y}-m{mi}" for s, x, y, mi in MATRIX])
+def test_merge_matrix(world, monkeypatch, sh, x, y, mi):
+    """A = rows [0, m) by route x, B = rows [m, n) by route y, exported and
+    merged into A. An EMPTY destination receives [0, m) as a blob too (from
+    the fused route) and must report the group count through nfilled with
+    no fetch in between."""
+    m = split_of(sh, mi)
+    exp, first = whole(world, monkeypatch, sh)
+    b = blob(world, monkeypatch, sh, y, m, sh.n)
+    a = partial(world, monkeypatch, sh, x, 0, m)
+    try:
+        if x == "EMPTY":
+            merge(a, blob(world, monkeypatch, sh, "FUSED", 0, m))
+        merge(a, b)
+        if x == "EMPTY":
+            assert a.nfilled == exp["ngroups"]
+        got = a.fetch(sorted=True)
+    finally:
+        a.free()
+    check_merged(sh, got, exp, first)
+
+
+THREE = [(S1, "FUSED", "DENSE", "SORTED"), (S1, "EMPTY", "DPIPE", "PART"),
+         (S2, "PART", "SORTED", "PIPE"), (S4, "SORTED", "FUSED", "PART"),
+         (SB[True], "EMPTY", "SORTED", "PIPE")]
+
+
+@gpu
+@pytest.mark.parametrize("sh,r0,r1,r2", THREE,
+                         ids=[f"{c[0]}-{c[1]}-{c[2]}-{c[3]}" for c in THREE])
+def test_three_way_merge_both_orders(world, monkeypatch, sh, r0, r1, r2):
+    """[0,4097), [4097,n/2), [n/2,n) from three routes into one destination,
+    merged in both orders: merge is commutative, integers identical."""
+    n = sh.n
+    exp, first = whole(world, monkeypatch, sh)
+    b1 = blob(world, monkeypatch, sh, r1, 4097, n // 2)
+    b2 = blob(world, monkeypatch, sh, r2, n // 2, n)
+    out = []
+    for order in ((b1, b2), (b2, b1)):
+        a = partial(world, monkeypatch, sh, r0, 0, 4097)
+        try:
+            if r0 == "EMPTY":
+                merge(a, blob(world, monkeypatch, sh, "PART", 0, 4097))
+            for b in order:
+                merge(a, b)
+            got = a.fetch(sorted=True)
+        finally:
+            a.free()
+        out.append(check_merged(sh, got, exp, first))
+    assert_same_ints(sh, out[0], out[1])
+
+
+@gpu
+@pytest.mark.parametrize("y", ["PART", "SORTED"])
+@pytest.mark.parametrize("sh", [S2, S4], ids=repr)
+def test_self_overlap_is_additive(world, monkeypatch, sh, y):
+    """The same blob merged twice into an empty result: COUNT/SUM exactly
+    twice the oracle of [m, n), MIN/MAX, AVG, keys and agg_has unchanged -
+    merge adds states, it does not dedup rows."""
+    m = sh.n // 2 + 1
+    exp, _ = whole(world, monkeypatch, sh, m, sh.n)
+    exp2 = dict(exp)
+    exp2["rows_passed"] = 2 * exp["rows_passed"]
+    exp2["agg_i"] = exp["agg_i"].copy()
+    exp2["agg_d"] = exp["agg_d"].copy()
+    for a, (name, _) in enumerate(sh.aggs):
+        if name in ("count_star", "count", "sum"):
+            exp2["agg_i"][a] *= 2
+            exp2["agg_d"][a] *= 2.0
+    b = blob(world, monkeypatch, sh, y, m, sh.n)
+    a = partial(world, monkeypatch, sh, "EMPTY", 0, 0)
+    try:
+        merge(a, b)
+        merge(a, b)
+        assert a.nfilled == exp["ngroups"]
+        got = a.fetch(sorted=True)
+    finally:
+        a.free()
+    check_merged(sh, got, exp2)
+
+
+def oracle_ngroups(world, monkeypatch, sh, rb, re_):
+    return whole(world, monkeypatch, sh, rb, re_)[0]["ngroups"]
+
+
+@gpu
+def test_capacity_regrow_from_1024_slots(world, monkeypatch):
+    """agg_empty(expected_groups=1) has 1024 slots. Shard 1 regrows it with
+    no own groups (own_n == 0), shard 2 regrows it again with own groups to
+    re-insert (own_n > 0), shard 3 merges in place. The slot arithmetic of
+    bkgpu_agg_merge is restated from the oracle's group counts so the test
+    fails if the shards stop triggering what they are here for."""
+    sh = SFLAT
+    n = sh.n
+    cuts = [0, 3000, n // 2, n]
+    exp, first = whole(world, monkeypatch, sh)
+    g = [oracle_ngroups(world, monkeypatch, sh, cuts[i], cuts[i + 1])
+         for i in range(3)]
+    g01 = oracle_ngroups(world, monkeypatch, sh, 0, cuts[2])
+
+    def pow2(x):
+        p = 1
+        while p < x:
+            p <<= 1
+        return p
+    assert (0 + g[0]) * 8 > 1024 * 7                       # regrow, own_n == 0
+    ns1 = pow2(g[0] * 2 + 1024)
+    assert g[0] > 0 and (g[0] + g[1]) * 8 > ns1 * 7        # regrow, own_n > 0
+    ns2 = pow2((g[0] + g[1]) * 2 + 1024)
+    assert (g01 + g[2]) * 8 <= ns2 * 7                     # merge in place
+    t, plan = plan_of(world, sh)
+    a = world.eng.agg_empty(plan, expected_groups=1)
+    try:
+        for i, route in enumerate(["SORTED", "PART", "DENSE"]):
+            merge(a, blob(world, monkeypatch, sh, route, cuts[i], cuts[i + 1]))
+            want = [g[0], g01, exp["ngroups"]][i]
+            assert a.nfilled == want, i
+        got = a.fetch(sorted=True)
+    finally:
+        a.free()
+    assert got["ngroups"] > 40_000
+    check_merged(sh, got, exp, first)
+
+
+@gpu
+def test_sorted_destination_rebuilds_on_every_merge(world, monkeypatch):
+    """A sort-dedup table is dense (nslots == ngroups, slot = group id - 1):
+    no merge may probe it as a hash table. An empty blob (n_groups == 0)
+    still rebuilds it and must leave the result unchanged."""
+    import torch
+    sh = SFLAT
+    h = sh.n // 2
+    exp_a, first_a = whole(world, monkeypatch, sh, 0, h)
+    exp, first = whole(world, monkeypatch, sh)
+    a = partial(world, monkeypatch, sh, "SORTED", 0, h)
+    try:
+        nothing = torch.zeros(64, dtype=torch.uint8, device="cuda")
+        a.merge_blob(nothing.data_ptr(), 0)
+        check_merged(sh, a.fetch(sorted=True), exp_a, first_a)
+        merge(a, blob(world, monkeypatch, sh, "PART", h, sh.n))
+        got = a.fetch(sorted=True)
+    finally:
+        a.free()
+    check_merged(sh, got, exp, first)
+
+
+@gpu
+def test_sorted_destination_with_no_rows(world, monkeypatch):
+    """filter_agg_sorted over a range whose rows all fail the filter: n == 0,
+    one unclaimed slot. Everything it holds afterwards comes from merges."""
+    sh = SFLAT
+    c0 = world.host_cols(sh)[0]
+    r = int(np.nonzero(c0[1:] >= K80)[0][0]) + 1      # first failing row >= 1
+    exp, first = whole(world, monkeypatch, sh)
+    a = partial(world, monkeypatch, sh, "SORTED", r, r + 1)
+    try:
+        assert a.rows_passed == 0 and a.ngroups == 0
+        merge(a, blob(world, monkeypatch, sh, "PART", r + 1, sh.n))
+        merge(a, blob(world, monkeypatch, sh, "FUSED", 0, r))
+        got = a.fetch(sorted=True)
+    finally:
+        a.free()
+    check_merged(sh, got, exp, first)
+
+
+# ---- 2. no GROUP BY ---------------------------------------------------------
+def _nogroup(sh, n):
+    return sh.clone(f"{sh.name}_nogroup_{n}", group=[], n=n, eg=1, dense=False)
+
+
+NOGROUP = [_nogroup(sh, n) for sh in (S1, S2) for n in (20, 300_000)]
+
+
+def _nopass(sh):
+    """same table (World caches tables by name: keep it) and aggregates, a
+    filter no row passes"""
+    return sh.clone(sh.name, conj=[(0, "<", -1)])
+
+
+def scalar(world, monkeypatch, sh, rb, re_, nopass=False):
+    t, plan = plan_of(world, _nopass(sh) if nopass else sh)
+    res = forced(monkeypatch, {},
+                 lambda: world.eng.filter_agg(t, plan, rb, re_,
+                                              expected_groups=1))
+    names = list(res.breakdown())
+    if names != FUSED:
+        res.free()
+    assert names == FUSED, names
+    return res
+
+
+@gpu
+@pytest.mark.parametrize("dest", ["scalar", "empty", "scalar_nopass"])
+@pytest.mark.parametrize("sh", NOGROUP, ids=repr)
+def test_nogroup_merge(world, monkeypatch, sh, dest):
+    """SELECT COUNT(*), SUM(x) ... without GROUP BY, sharded and merged. The
+    single group lives in slot 0 of every table (bkgpu.h); at the parent
+    commit k_merge_blob placed the peer's group by key_hash (slot 46 of 1024)
+    next to a pre-claimed slot 0 and compact kept one of the two. A shard
+    whose filter passes no rows carries the zero state: a no-op."""
+    n = sh.n
+    m = 7 if n == 20 else n // 2 + 1
+    exp, first = whole(world, monkeypatch, sh)
+    srcs = []
+    try:
+        if dest == "scalar":
+            a = scalar(world, monkeypatch, sh, 0, m)
+        elif dest == "scalar_nopass":
+            a = scalar(world, monkeypatch, sh, 0, n, nopass=True)
+            srcs.append(scalar(world, monkeypatch, sh, 0, m))
+        else:
+            _, plan = plan_of(world, sh)
+            a = world.eng.agg_empty(plan, expected_groups=1)
+            srcs.append(scalar(world, monkeypatch, sh, 0, m))
+        srcs.append(a)
+        srcs.append(scalar(world, monkeypatch, sh, m, n))
+        srcs.append(scalar(world, monkeypatch, sh, 0, n, nopass=True))
+        for s in srcs:
+            if s is not a:
+                assert s.ngroups == 1
+                merge(a, export(s))
+        assert a.nfilled == 1
+        assert a.ngroups == 1
+        got = a.fetch(sorted=True)
+    finally:
+        for s in srcs:
+            s.free()
+    check_merged(sh, got, exp, first)
+
+
+@gpu
+@pytest.mark.parametrize("sh", NOGROUP, ids=repr)
+def test_nogroup_all_shards_empty(world, monkeypatch, sh):
+    """SUM / MIN / MAX stay NULL only if every shard was empty"""
+    npz = sh.clone(sh.name + "_nopass", conj=[(0, "<", -1)])
+    exp, first = whole(world, monkeypatch, npz)
+    assert exp["ngroups"] == 1 and exp["rows_passed"] == 0
+    a = scalar(world, monkeypatch, sh, 0, 7, nopass=True)
+    b = scalar(world, monkeypatch, sh, 7, sh.n, nopass=True)
+    try:
+        merge(a, export(b))
+        assert a.ngroups == 1
+        got = a.fetch(sorted=True)
+    finally:
+        a.free()
+        b.free()
+    check_merged(npz, got, exp, first)
+    for i, (name, _) in enumerate(sh.aggs):
+        assert got["agg_has"][i][0] == (1 if name.startswith("count") else 0)
+
+
+# ---- 3. hash-partitioned exchange against the oracle -------------------------
+def exchange_source(world, monkeypatch, sh, form, re_):
+    if form != "MERGED":
+        return partial(world, monkeypatch, sh, form, 0, re_)
+    a = partial(world, monkeypatch, sh, "PART", 0, re_ // 2)
+    merge(a, blob(world, monkeypatch, sh, "SORTED", re_ // 2, re_))
+    return a
+
+
+def read_part(buf, cnt, naggs):
+    """host (flags, k0, k1) of a part blob laid out for cnt groups"""
+    raw = buf.cpu().numpy()
+    flags = raw[:cnt * 4].view(np.uint32)
+    k0 = raw[cnt * 4:cnt * 12].view(np.uint64)
+    k1 = raw[cnt * 12:cnt * 20].view(np.uint64)
+    assert len(raw) >= cnt * (20 + 16 * naggs)
+    return flags, k0, k1
+
+
+EXCH = ([(sh, f) for sh in (S2, S4) for f in ("PART", "SORTED", "MERGED")] +
+        [(S1, "DENSE")])     # S2 and S4 are not dense-eligible
+
+
+@gpu
+@pytest.mark.parametrize("nparts", [1, 2, 7, 16384])
+@pytest.mark.parametrize("sh,form", EXCH,
+                         ids=[f"{s}-{f}" for s, f in EXCH])
+def test_exchange_parts_union_equals_oracle(world, monkeypatch, sh, form,
+                                            nparts):
+    """part_counts / export_part / agg_empty + merge: the parts partition the
+    result (counts add up, every blob is full, no key in two parts) and
+    their merged union is the oracle's whole-range result. 16384 parts run
+    on a 400-row range (a few hundred groups), only its non-empty parts."""
+    import torch
+    re_ = 400 if nparts == 16384 else sh.n
+    exp, first = whole(world, monkeypatch, sh, 0, re_)
+    assert nparts < 16384 or 0 < exp["ngroups"] <= 2000
+    naggs = len(sh.aggs)
+    per_group = 20 + 16 * naggs
+    _, plan = plan_of(world, sh)
+    res = exchange_source(world, monkeypatch, sh, form, re_)
+    fetches, keys = [], []
+    try:
+        counts = res.part_counts(nparts)
+        assert len(counts) == nparts
+        assert sum(counts) == res.ngroups == exp["ngroups"]
+        for p in np.nonzero(counts)[0]:
+            cnt = counts[p]
+            buf = torch.full((cnt * per_group,), 0xFF, dtype=torch.uint8,
+                             device="cuda")
+            res.export_part(nparts, int(p), buf.data_ptr(), cnt)
+            flags, k0, k1 = read_part(buf, cnt, naggs)
+            # flag words are <= 0xFF: an untouched 0xFFFFFFFF entry means the
+            # part held fewer than counts[p] groups
+            assert not np.any(flags == 0xFFFFFFFF), p
+            keys.append(np.stack([flags.astype(np.uint64), k0, k1], axis=1))
+            part = world.eng.agg_empty(plan, expected_groups=cnt)
+            try:
+                part.merge_blob(buf.data_ptr(), cnt)
+                assert part.nfilled == cnt
+                fetches.append(part.fetch(sorted=True))
+            finally:
+                part.free()
+    finally:
+        res.free()
+    keys = np.concatenate(keys)
+    assert len(np.unique(keys, axis=0)) == len(keys) == exp["ngroups"]
+    enc = np.concatenate([f["enc"] for f in fetches])
+    flags = np.concatenate([f["flags"] for f in fetches])
+    # canonical order: flags, then each non-null key's encoding (a null
+    # key's encoding is 0 on both sides of a comparison)
+    order = np.lexsort(tuple(enc[:, k] for k in range(BK_MAX_GROUP - 1, -1, -1))
+                       + (flags,))
+    got = {"ngroups": len(flags), "flags": flags[order], "enc": enc[order]}
+    for k in ("agg_i", "agg_d", "agg_has"):
+        got[k] = np.concatenate([f[k] for f in fetches], axis=1)[:, order]
+    check_merged(sh, got, exp, first)
+
+
+@gpu
+def test_exchange_rejects_bad_nparts(world, monkeypatch):
+    import torch
+    res = partial(world, monkeypatch, S4, "PART", 0, 400)
+    buf = torch.zeros(res.ngroups * (20 + 16 * len(S4.aggs)),
+                      dtype=torch.uint8, device="cuda")
+    try:
+        for nparts in (0, 16385):
+            with pytest.raises(RuntimeError):
+                res.part_counts(nparts)
+            with pytest.raises(RuntimeError):
+                res.export_part(nparts, 0, buf.data_ptr(), res.ngroups)
+    finally:
+        res.free()
+
+
+@gpu
+@pytest.mark.parametrize("form,nparts,re_", [("PART", 2, None),
+                                             ("SORTED", 7, None),
+                                             ("PART", 16384, 400)])
+def test_export_part_undersized_part_groups_is_an_error(world, monkeypatch,
+                                                        form, nparts, re_):
+    """The buffer has the TRUE size (nothing can be written out of range);
+    only the part_groups argument is one short. At the parent commit the
+    call returned 0 and the blob silently lacked a group. With 16384 parts
+    the part holds one group, so part_groups is 0."""
+    import torch
+    sh = S4
+    res = partial(world, monkeypatch, sh, form, 0, re_ or sh.n)
+    try:
+        counts = np.array(res.part_counts(nparts))
+        p = int(np.nonzero(counts == 1 if nparts == 16384 else counts > 1)
+                [0][0])
+        cnt = int(counts[p])
+        buf = torch.zeros(cnt * (20 + 16 * len(sh.aggs)), dtype=torch.uint8,
+                          device="cuda")
+        with pytest.raises(RuntimeError, match="part_groups"):
+            res.export_part(nparts, p, buf.data_ptr(), cnt - 1)
+        res.export_part(nparts, p, buf.data_ptr(), cnt)     # exact: fine
+    finally:
+        res.free()
+
+
+# ---- 4. wire format ----------------------------------------------------------
+def dec_i64(u):
+    return (u ^ np.uint64(1 << 63)).view(np.int64)
+
+
+def dec_f64(u):
+    neg = (u >> np.uint64(63)) == 0
+    bits = np.where(neg, ~u, u & np.uint64((1 << 63) - 1))
+    return bits.view(np.float64)
+
+
+@gpu
+def test_wire_format(world, monkeypatch):
+    """Decode an exported blob on the host exactly as include/bkgpu.h
+    documents it and recompute every finalized value from the raw states:
+    [flags u32*n][k0 u64*n][k1 u64*n][states u64*n*2*naggs], MIN carrying
+    the COMPLEMENT of the order encoding."""
+    sh = S2
+    exp, first = whole(world, monkeypatch, sh)
+    res = partial(world, monkeypatch, sh, "PART", 0, sh.n)
+    try:
+        buf, n = export(res)
+        nbytes = res.export_bytes()
+        fetched = res.fetch(sorted=True)
+    finally:
+        res.free()
+    na = len(sh.aggs)
+    assert n == exp["ngroups"] and nbytes == n * (20 + 16 * na)
+    raw = buf.cpu().numpy()[:nbytes]
+    flags = raw[:4 * n].view(np.uint32)
+    k0 = raw[4 * n:12 * n].view(np.uint64)
+    k1 = raw[12 * n:20 * n].view(np.uint64)
+    st = raw[20 * n:].view(np.uint64).reshape(n, 2 * na)
+    order = np.lexsort((k1, k0, flags))
+    got = {"ngroups": n, "rows_passed": exp["rows_passed"],
+           "flags": flags[order].astype(np.uint8),
+           "enc": np.zeros((n, BK_MAX_GROUP), np.uint64),
+           "agg_i": np.zeros((na, n), np.int64),
+           "agg_d": np.zeros((na, n), np.float64),
+           "agg_has": np.zeros((na, n), np.uint8)}
+    assert np.all(flags <= 0xFF)
+    got["enc"][:, 0] = k0[order]      # no declared group_bits: raw encodings
+    got["enc"][:, 1] = k1[order]
+    for a, (name, col) in enumerate(sh.aggs):
+        val, cnt = st[order, 2 * a], st[order, 2 * a + 1]
+        is_d = col >= 0 and sh.ct[col] == 12
+        has = cnt > 0
+        if name in ("count_star", "count"):
+            got["agg_i"][a] = val.view(np.int64)
+            has = np.ones(n, bool)
+        elif name == "sum":
+            if is_d:
+                got["agg_d"][a] = np.where(has, val.view(np.float64), 0.0)
+            else:
+                got["agg_i"][a] = np.where(has, val.view(np.int64), 0)
+        elif name == "avg":
+            got["agg_d"][a] = np.where(
+                has, val.view(np.float64) / np.maximum(cnt, 1), 0.0)
+        else:
+            e = ~val if name == "min" else val
+            if is_d:
+                got["agg_d"][a] = np.where(has, dec_f64(e), 0.0)
+            else:
+                got["agg_i"][a] = np.where(has, dec_i64(e), 0)
+        got["agg_has"][a] = has
+    check_merged(sh, got, exp, first)
+    for k in ("flags", "enc", "agg_i", "agg_d", "agg_has"):
+        assert np.array_equal(got[k], fetched[k]), k
+
+
+# ---- 5. DISTINCT across shards ------------------------------------------------
+DN = 200_000
+
+
+class DShape:
+    """COUNT(DISTINCT d), SUM(DISTINCT d), a plain SUM and MIN; d in [0,300)
+    so both shards hold nearly every (g, d) pair"""
+
+    def __init__(self, name, group, d_null):
+        self.name, self.group = name, group
+        self.specs = [(I64, D_UNI, 0, 64, 0), (I64, D_UNI, 0, 300, d_null),
+                      (I64, D_UNI, 0, 1000, 0), (I64, D_UNI, 0, 1 << 31, 0)]
+        self.conj = [(3, "<", 1 << 30)]
+        self.aggs = [("count_star", -1), ("count_distinct", 1),
+                     ("sum_distinct", 1), ("sum", 2), ("min", 2)]
+        self.ct = [s[0] for s in self.specs]
+
+    def __repr__(self):
+        return self.name
+
+
+# nullable d runs k_rollup's d_null path; dense_eligible() refuses nullable
+# keys, so the dense + dense form has a sibling shape with d NOT NULL
+D_KEY = DShape("d_key", [0], 150_000)
+D_NOKEY = DShape("d_nokey", [], 150_000)
+D_KEY_NN = DShape("d_key_notnull", [0], 0)
+D_NOKEY_NN = DShape("d_nokey_notnull", [], 0)
+DCASES = ([(sh, fa, fb) for sh in (D_KEY, D_NOKEY)
+           for fa, fb in (("PART", "PART"), ("SORTED", "PART"),
+                          ("PART", "SORTED"))] +
+          [(D_KEY_NN, "DENSE", "DENSE"), (D_NOKEY_NN, "DENSE", "DENSE")])
+
+
+class DWorld:
+    def __init__(self, eng, orc):
+        self.eng, self.orc = eng, orc
+        self.tables, self.host, self.exp = {}, {}, {}
+
+    def table(self, sh):
+        if sh.name not in self.tables:
+            t = self.eng.create_table(sh.specs, DN)
+            self.eng.generate(t, SEED)
+            self.tables[sh.name] = t
+        return self.tables[sh.name]
+
+    def plan(self, sh):
+        from baikaldb_amd import QueryPlan
+        return QueryPlan(self.table(sh).col_types, conjuncts=sh.conj,
+                         group=sh.group, aggs=sh.aggs)
+
+    def queries(self, sh):
+        l1_plan, _, src_idx = self.plan(sh).split_distinct()
+        oconj = [(c, OPS[op], I64, lit, 0, 0) for c, op, lit in sh.conj]
+        q1 = make_query(oconj, l1_plan.group,
+                        [(AGGMAP[a], c) for a, c in l1_plan.aggs], sh.ct)
+        q2 = make_query((), sh.group, [(AGGMAP[a], c) for a, c in sh.aggs],
+                        sh.ct)
+        return q1, q2, src_idx
+
+    def cols(self, sh):
+        if sh.name not in self.host:
+            from oracle import BkColSpec
+            arr = (BkColSpec * len(sh.specs))()
+            for i, s in enumerate(sh.specs):
+                (arr[i].col_type, arr[i].dist, arr[i].p0, arr[i].p1,
+                 arr[i].null_frac_x1e6) = s
+            self.host[sh.name] = self.orc.generate_table(list(arr), DN, SEED)
+        return self.host[sh.name]
+
+    def expected(self, sh, rb=0, re_=DN):
+        key = (sh.name, rb, re_)
+        if key not in self.exp:
+            cols, valids = self.cols(sh)
+            q1, q2, src_idx = self.queries(sh)
+            self.exp[key] = self.orc.filter_agg_distinct(
+                cols, valids, sh.ct, q1, q2, src_idx, nthreads=4,
+                dict_seed=SEED, row_begin=rb, row_end=re_)
+        return self.exp[key]
+
+    def level1_keys(self, sh, rb, re_):
+        cols, valids = self.cols(sh)
+        q1 = self.queries(sh)[0]
+        r = self.orc.filter_agg(cols, valids, sh.ct, q1, nthreads=4,
+                                dict_seed=SEED, row_begin=rb, row_end=re_)
+        return set(zip(r["flags"].tolist(), r["enc"][:, 0].tolist(),
+                       r["enc"][:, 1].tolist()))
+
+    def level1(self, monkeypatch, sh, form, rb, re_):
+        l1_plan = self.plan(sh).split_distinct()[0]
+        t = self.table(sh)
+        knobs, names = ROUTES[form]
+        if form == "SORTED":
+            res = forced(monkeypatch, knobs,
+                         lambda: self.eng.filter_agg_sorted(t, l1_plan, rb,
+                                                            re_))
+        else:
+            res = forced(monkeypatch, knobs,
+                         lambda: self.eng.filter_agg(t, l1_plan, rb, re_,
+                                                     expected_groups=1 << 16))
+        got = list(res.breakdown())
+        if got != names:
+            res.free()
+        assert got == names, (form, got)
+        return res
+
+    def rollup(self, sh, l1):
+        from baikaldb_amd.engine import AggResult
+        plan = self.plan(sh)
+        _, q2, src_idx = plan.split_distinct()
+        h = self.eng.lib.bkgpu_agg_rollup(l1.handle, C.byref(q2), src_idx,
+                                          1 << 12)
+        assert h, self.eng.lib.bkgpu_last_error().decode()
+        return AggResult(self.eng, h, plan)
+
+    def close(self):
+        for t in self.tables.values():
+            t.free()
+        self.tables.clear()
+
+
+@pytest.fixture(scope="module")
+def dworld(eng, orc):
+    w = DWorld(eng, orc)
+    yield w
+    w.close()
+
+
+def check_distinct(sh, got, exp):
+    assert int(got["agg_i"][0].sum()) == exp["rows_passed"]
+    g = dict(got)
+    g["rows_passed"] = exp["rows_passed"]    # rollup reports its level 1's
+    assert_parity(g, exp, _parity_names(sh.aggs), sh.ct)
+    # every aggregate here is an integer: assert_parity compared agg_i exactly
+
+
+@gpu
+@pytest.mark.parametrize("sh,fa,fb", DCASES,
+                         ids=[f"{s}-{a}+{b}" for s, a, b in DCASES])
+def test_distinct_across_shards(dworld, monkeypatch, sh, fa, fb):
+    """The documented multi-GPU flow for DISTINCT (bkgpu.h): exchange LEVEL-1
+    blobs - the merge dedups (g, d) pairs - then roll up."""
+    m = DN // 2 + 1
+    ka, kb = dworld.level1_keys(sh, 0, m), dworld.level1_keys(sh, m, DN)
+    # a merge that failed to dedup would go unnoticed on disjoint shards
+    assert len(ka & kb) * 4 >= len(ka | kb)
+    exp = dworld.expected(sh)
+    a = dworld.level1(monkeypatch, sh, fa, 0, m)
+    b = dworld.level1(monkeypatch, sh, fb, m, DN)
+    res = None
+    try:
+        merge(a, export(b))
+        assert a.ngroups == len(ka | kb)
+        res = dworld.rollup(sh, a)
+        got = res.fetch(sorted=True)
+    finally:
+        a.free()
+        b.free()
+        if res is not None:
+            res.free()
+    assert got["ngroups"] == (1 if not sh.group else exp["ngroups"])
+    check_distinct(sh, got, exp)
+
+
+@gpu
+def test_nogroup_rollup_output_as_merge_destination(dworld, monkeypatch):
+    """A rollup output without user keys is a scalar slot-0 table too.
+    Level-2 states merge additively (only level-1 blobs dedup), so after
+    merging the other range's rollup COUNT(*), SUM and MIN are the oracle's
+    whole-range values and the DISTINCT aggregates the sum of the oracle's
+    per-range values."""
+    sh = D_NOKEY
+    m = DN // 2 + 1
+    exp, e0, e1 = (dworld.expected(sh), dworld.expected(sh, 0, m),
+                   dworld.expected(sh, m, DN))
+    l0 = dworld.level1(monkeypatch, sh, "PART", 0, m)
+    l1 = dworld.level1(monkeypatch, sh, "SORTED", m, DN)
+    r0 = r1 = None
+    try:
+        r0, r1 = dworld.rollup(sh, l0), dworld.rollup(sh, l1)
+        assert r1.ngroups == 1
+        merge(r0, export(r1))
+        assert r0.nfilled == 1 and r0.ngroups == 1
+        got = r0.fetch(sorted=True)
+    finally:
+        for r in (l0, l1, r0, r1):
+            if r is not None:
+                r.free()
+    want = dict(exp)
+    want["agg_i"] = exp["agg_i"].copy()
+    for a in (1, 2):                       # count_distinct, sum_distinct
+        want["agg_i"][a] = e0["agg_i"][a] + e1["agg_i"][a]
+    assert want["agg_i"][1][0] > exp["agg_i"][1][0]     # shards do overlap
+    check_distinct(sh, got, want)
+
+
+# ---- 6. fetch(max_groups) ------------------------------------------------------
+def raw_fetch(res, k, na):
+    """bkgpu_agg_fetch with max_groups = k passed through unclamped
+    (AggResult.fetch clamps to ngroups in Python)"""
+    cap = max(k, 1)
+    flags = np.zeros(cap, np.uint8)
+    enc = np.zeros(cap * BK_MAX_GROUP, np.uint64)
+    out_i = np.zeros(na * cap, np.int64)
+    out_d = np.zeros(na * cap, np.float64)
+    out_has = np.zeros(na * cap, np.uint8)
+    got = res.engine.lib.bkgpu_agg_fetch(
+        res.handle, 1, k, flags.ctypes.data_as(C.POINTER(C.c_uint8)),
+        enc.ctypes.data_as(C.POINTER(C.c_uint64)),
+        out_i.ctypes.data_as(C.POINTER(C.c_int64)),
+        out_d.ctypes.data_as(C.POINTER(C.c_double)),
+        out_has.ctypes.data_as(C.POINTER(C.c_uint8)))
+    got = int(got)
+    assert got >= 0
+    return {"ngroups": got, "flags": flags[:got],
+            "enc": enc[:got * BK_MAX_GROUP].reshape(got, BK_MAX_GROUP),
+            "agg_i": out_i[:na * got].reshape(na, got),
+            "agg_d": out_d[:na * got].reshape(na, got),
+            "agg_has": out_has[:na * got].reshape(na, got)}
+
+
+@gpu
+@pytest.mark.parametrize("route", ["PART", "DENSE", "SORTED"])
+def test_fetch_max_groups_is_a_prefix(world, monkeypatch, route):
+    """the first min(k, ngroups) rows of the full sorted fetch, every array;
+    the aggregate arrays are laid out with stride out_n, not ngroups"""
+    sh = S1
+    rb, re_ = 7, sh.n - 3
+    exp, first = whole(world, monkeypatch, sh, rb, re_)
+    na = len(sh.aggs)
+    res = partial(world, monkeypatch, sh, route, rb, re_)
+    try:
+        full = res.fetch(sorted=True)
+        ng = full["ngroups"]
+        assert ng == exp["ngroups"] > 5
+        cuts = {k: raw_fetch(res, k, na) for k in (0, 1, ng - 1, ng, ng + 5)}
+    finally:
+        res.free()
+    check_result(sh, full, exp)
+    assert_same_ints(sh, full, first)
+    for k, got in cuts.items():
+        c = min(k, ng)
+        assert got["ngroups"] == c, k
+        assert np.array_equal(got["flags"], full["flags"][:c]), k
+        assert np.array_equal(got["enc"], full["enc"][:c]), k
+        for name in ("agg_i", "agg_d", "agg_has"):
+            assert np.array_equal(got[name], full[name][:, :c]), (k, name)
