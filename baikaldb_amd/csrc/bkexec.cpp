@@ -180,6 +180,7 @@ public:
     }
     int n_conjuncts() const { return _n_conjuncts; }
     const BkConjunct* conjuncts() const { return _conjuncts; }
+    bool is_having() const { return _node_type == BK_HAVING_FILTER_NODE; }
     /* As the EFFECTIVE ROOT (SELECT without GROUP BY/ORDER BY) FilterNode
      * emits the passing rows itself (filter_node.cpp:736-795): the GPU
      * filter runs over BOUNDED row-range chunks (BK_FETCH_CHUNK rows,
@@ -187,7 +188,11 @@ public:
      * scanning the next range, so host memory stays O(chunk) for a
      * filter-only SELECT over any table size — the streamed analogue of
      * the reference scan's batch iterator (rocksdb_scan_node.cpp
-     * get_next loop), not a whole-result materialization. */
+     * get_next loop), not a whole-result materialization.
+     * A HAVING_FILTER_NODE root streams the same way over the aggregate's
+     * materialized table (source_of): rows in canonical group order, slot
+     * layout and type tags of the AGG root. */
+    int open(RuntimeState* state) override;
     int get_next(RuntimeState* state, RowBatch* batch, bool* eos) override;
     int n_slots();  /* lazily resolved from the scan's table */
     void close(RuntimeState* state) override {
@@ -195,6 +200,7 @@ public:
         _opened = false;
         _eos_source = false;
         _scan_pos = 0;
+        _src_table = nullptr;
         _rowids.clear();
         _cols_i.clear(); _cols_d.clear(); _cols_n.clear();
         _iter = 0;
@@ -203,6 +209,10 @@ private:
     int fetch_chunk(RuntimeState* state);  /* 1 = chunk ready, 0 = drained */
     int32_t _n_conjuncts = 0;
     BkConjunct _conjuncts[BK_MAX_CONJUNCTS] = {};
+    /* HAVING root: the aggregate's materialized table + every HAVING
+     * conjunct of the chain (set by open) */
+    BkgTable* _src_table = nullptr;
+    BkQuerySpec _src_q{};
     bool _opened = false;
     bool _eos_source = false;
     int _ncols = 0;
@@ -219,13 +229,19 @@ private:
 /* helpers to locate the pipeline pieces below a blocking node */
 static ScanNode* find_scan(ExecNode* n);
 
-int FilterNode::n_slots() {
-    if (_ncols == 0) {
-        ScanNode* scan = find_scan(this);
-        if (scan) _ncols = bkgpu_table_ncols(scan->table());
-    }
-    return _ncols;
-}
+/* What a blocking node consumes (SortNode / WindowNode / AggNode / a HAVING
+ * root): walking the single-child chain below `node`,
+ *  - an AGG_NODE / MERGE_AGG_NODE met before the scan makes the source that
+ *    AggNode's materialized table (canonical group order) under the
+ *    conjuncts of the HAVING_FILTER_NODEs passed on the way; columns are
+ *    then slot indices into [group keys...][agg outputs...];
+ *  - otherwise it is the scan's table under the WHERE filter. */
+struct Source {
+    BkgTable* table = nullptr;
+    bool from_agg = false;
+    BkQuerySpec q{};          /* only n_conjuncts / conjuncts are set */
+};
+static int source_of(ExecNode* node, RuntimeState* state, Source* src);
 
 static int64_t fetch_chunk_rows() {
     /* read per chunk (once every few million rows), not cached, so a
@@ -236,9 +252,12 @@ static int64_t fetch_chunk_rows() {
 }
 
 int FilterNode::fetch_chunk(RuntimeState* state) {
-    ScanNode* scan = find_scan(this);
-    if (!scan) { state->error_msg = "FilterNode: no scan below"; return -1; }
-    BkgTable* t = scan->table();
+    BkgTable* t = _src_table;
+    if (!t) {
+        ScanNode* scan = find_scan(this);
+        if (!scan) { state->error_msg = "FilterNode: no scan below"; return -1; }
+        t = scan->table();
+    }
     if (!_opened) {
         _nrows = bkgpu_table_nrows(t);
         _ncols = bkgpu_table_ncols(t);
@@ -254,6 +273,7 @@ int FilterNode::fetch_chunk(RuntimeState* state) {
     BkQuerySpec q{};
     q.n_conjuncts = _n_conjuncts;
     memcpy(q.conjuncts, _conjuncts, sizeof(q.conjuncts));
+    if (_src_table) q = _src_q;
     const int64_t chunk = fetch_chunk_rows();
     while (_scan_pos < _nrows) {
         int64_t end = std::min(_nrows, _scan_pos + chunk);
@@ -267,8 +287,10 @@ int FilterNode::fetch_chunk(RuntimeState* state) {
          * chunks advance in row order, so sorting within the chunk keeps
          * the global stream ordered. */
         std::sort(_rowids.begin(), _rowids.end());
-        state->inc_num_scan_rows(span);
-        state->inc_num_filter_rows(span - got);
+        if (!_src_table) {   /* HAVING-rejected groups are not scan rows */
+            state->inc_num_scan_rows(span);
+            state->inc_num_filter_rows(span - got);
+        }
         _scan_pos = end;
         if (got == 0) continue;
         for (int c = 0; c < _ncols; c++) {
@@ -325,17 +347,6 @@ static ScanNode* find_scan(ExecNode* n) {
     }
     return nullptr;
 }
-static FilterNode* find_filter(ExecNode* n) {
-    if (!n) return nullptr;
-    if (n->node_type() == BK_TABLE_FILTER_NODE ||
-        n->node_type() == BK_WHERE_FILTER_NODE)
-        return static_cast<FilterNode*>(n);
-    for (auto c : n->children()) {
-        FilterNode* f = find_filter(c);
-        if (f) return f;
-    }
-    return nullptr;
-}
 
 struct FetchedGroups {
     int64_t n = 0;
@@ -370,19 +381,77 @@ public:
         _desc = node;
         return 0;
     }
+    ~AggNode() override { if (_result) bkgpu_table_free(_result); }
     int open(RuntimeState* state) override {
+        /* already drained as a table by the node above (result_table) */
+        if (_result) return 0;
+        return run(state, /*want_table=*/false);
+    }
+    /* The finished aggregate as a device-resident table of finalized values
+     * in canonical group order, slots [group keys...][agg outputs...] —
+     * what a HAVING / SORT / WINDOW / AGG node above consumes (source_of).
+     * Runs the pipeline open() runs but keeps the result on the device
+     * (bkgpu_agg_to_table) instead of fetching it. Lives until close(). */
+    BkgTable* result_table(RuntimeState* state) {
+        if (!_result && run(state, /*want_table=*/true) < 0) return nullptr;
+        return _result;
+    }
+private:
+    /* multi-column DISTINCT stitches its passes on the host: upload the
+     * stitched columns as the materialized table */
+    int upload_result(RuntimeState* state) {
+        const int nc = n_slots();
+        const int64_t n = _g.n;
+        BkColSpec specs[BK_MAX_GROUP + BK_MAX_AGGS] = {};
+        std::vector<std::vector<uint8_t>> valid(nc, std::vector<uint8_t>(n ? n : 1, 1));
+        std::vector<std::vector<int64_t>> data(nc, std::vector<int64_t>(n ? n : 1, 0));
+        for (int c = 0; c < nc; c++) {
+            const bool key = c < _q.n_group;
+            const int a = c - _q.n_group;
+            const int32_t ty = key ? _q.group_types[c]
+                : agg_out_type(_q.aggs[a].agg_type, _q.agg_in_types[a]);
+            specs[c].col_type = ty;
+            int32_t* d32 = (int32_t*)data[c].data();
+            for (int64_t g = 0; g < n; g++) {
+                bool has;
+                int64_t vi = 0;
+                if (key) {
+                    has = !((_g.flags[g] >> (7 - c)) & 1);
+                    uint64_t e = _g.enc[g * BK_MAX_GROUP + c];
+                    if (ty == BK_DOUBLE) { double d = bk_dec_f64(e); memcpy(&vi, &d, 8); }
+                    else if (ty == BK_STRING) vi = (int64_t)(uint32_t)e;
+                    else vi = bk_dec_i64(e);
+                } else {
+                    size_t idx = (size_t)a * n + g;
+                    has = _g.out_has[idx] != 0;
+                    if (ty == BK_DOUBLE) memcpy(&vi, &_g.out_d[idx], 8);
+                    else vi = _g.out_i[idx];
+                }
+                if (!has) { vi = 0; valid[c][g] = 0; specs[c].null_frac_x1e6 = 1; }
+                if (ty == BK_STRING) d32[g] = (int32_t)vi; else data[c][g] = vi;
+            }
+        }
+        _result = bkgpu_table_create(nc, specs, n);
+        if (!_result) { state->error_msg = bkgpu_last_error(); return -1; }
+        for (int c = 0; c < nc; c++)
+            if (bkgpu_table_upload(_result, c, data[c].data(),
+                                   specs[c].null_frac_x1e6 ? valid[c].data()
+                                                           : nullptr) != 0) {
+                state->error_msg = bkgpu_last_error();
+                return -1;
+            }
+        return 0;
+    }
+    int run(RuntimeState* state, bool want_table) {
+        /* resolve the source first: an aggregate below is drained as a
+         * table here, so the generic child open() finds it already done */
+        Source source;
+        if (source_of(this, state, &source) < 0) return -1;
         int ret = ExecNode::open(state);
         if (ret < 0) return ret;
-        ScanNode* scan = find_scan(this);
-        if (!scan) { state->error_msg = "AggNode: no scan below"; return -1; }
-        FilterNode* filter = find_filter(this);
-        BkQuerySpec q{};
-        if (filter) {
-            q.n_conjuncts = filter->n_conjuncts();
-            memcpy(q.conjuncts, filter->conjuncts(), sizeof(q.conjuncts));
-        }
+        BkQuerySpec q = source.q;
         q.n_group = _desc.n_group;
-        BkgTable* t = scan->table();
+        BkgTable* t = source.table;
         for (int k = 0; k < q.n_group; k++) {
             q.group_cols[k] = _desc.group_cols[k];
             q.group_types[k] = bkgpu_table_col_type(t, _desc.group_cols[k]);
@@ -432,6 +501,13 @@ public:
         std::vector<Src> src(q.n_aggs);
         std::vector<BkgAggOut*> outs;
         int64_t nrows_t = bkgpu_table_nrows(t);
+        if (source.from_agg && nrows_t == 0 && q.n_group > 0) {
+            /* no groups below: empty result, no kernel (without GROUP BY
+             * the pipeline still runs: it yields the one all-identity row) */
+            _g = FetchedGroups{};
+            _iter = 0;
+            return want_table ? upload_result(state) : 0;
+        }
         if (!has_distinct) {
             BkgAggOut* out = bkgpu_filter_agg(t, &q, 0, nrows_t, expected);
             if (!out) { state->error_msg = bkgpu_last_error(); return -1; }
@@ -516,8 +592,18 @@ public:
                 outs.push_back(r);
             }
         }
-        state->inc_num_scan_rows(nrows_t);
-        state->inc_num_filter_rows(nrows_t - bkgpu_agg_rows_passed(outs[0]));
+        if (!source.from_agg) {
+            /* over a materialized aggregate the counters stay what the
+             * inner AggNode set: groups are not scan rows */
+            state->inc_num_scan_rows(nrows_t);
+            state->inc_num_filter_rows(nrows_t - bkgpu_agg_rows_passed(outs[0]));
+        }
+        if (want_table && !has_distinct) {
+            _result = bkgpu_agg_to_table(outs[0], t, /*canonical=*/1);
+            if (!_result) state->error_msg = bkgpu_last_error();
+            bkgpu_agg_free(outs[0]);
+            return _result ? 0 : -1;
+        }
         /* fetch every pass in canonical key order; group sets align (same
          * filter + same user keys), assemble the output columns */
         int64_t n = bkgpu_agg_ngroups(outs[0]);
@@ -568,8 +654,9 @@ public:
         for (auto* o : outs) bkgpu_agg_free(o);
         _g.n = got;
         _iter = 0;
-        return 0;
+        return want_table ? upload_result(state) : 0;
     }
+public:
     int get_next(RuntimeState* state, RowBatch* batch, bool* eos) override {
         while (true) {
             if (state->is_cancelled()) { *eos = true; return 0; } /* agg_node.cpp:450 */
@@ -613,15 +700,102 @@ public:
         ExecNode::close(state);
         _g = FetchedGroups{};
         _iter = 0;
+        if (_result) { bkgpu_table_free(_result); _result = nullptr; }
     }
-    int n_slots() const { return _q.n_group + _q.n_aggs; }
+    int n_slots() const { return _desc.n_group + _desc.n_aggs; }
     const BkQuerySpec& spec() const { return _q; }
 private:
     BkPlanNodeDesc _desc{};
     BkQuerySpec _q{};
     FetchedGroups _g;
     int64_t _iter = 0;
+    BkgTable* _result = nullptr;   /* materialized table (result_table) */
 };
+
+static bool is_agg_node(const ExecNode* n) {
+    return n->node_type() == BK_AGG_NODE || n->node_type() == BK_MERGE_AGG_NODE;
+}
+
+static int source_of(ExecNode* node, RuntimeState* state, Source* src) {
+    FilterNode* where = nullptr;
+    int n_having = 0;
+    BkConjunct having[BK_MAX_CONJUNCTS];
+    for (ExecNode* n = node->children().empty() ? nullptr : node->children()[0];
+         n; n = n->children().empty() ? nullptr : n->children()[0]) {
+        const int32_t ty = n->node_type();
+        if (ty == BK_HAVING_FILTER_NODE) {
+            FilterNode* f = static_cast<FilterNode*>(n);
+            if (n_having + f->n_conjuncts() > BK_MAX_CONJUNCTS) {
+                state->error_msg = "too many HAVING conjuncts";
+                return -1;
+            }
+            for (int i = 0; i < f->n_conjuncts(); i++)
+                having[n_having++] = f->conjuncts()[i];
+        } else if (ty == BK_TABLE_FILTER_NODE || ty == BK_WHERE_FILTER_NODE) {
+            if (!where) where = static_cast<FilterNode*>(n);
+        } else if (is_agg_node(n)) {
+            src->table = static_cast<AggNode*>(n)->result_table(state);
+            if (!src->table) return -1;
+            src->from_agg = true;
+            src->q.n_conjuncts = n_having;
+            memcpy(src->q.conjuncts, having, sizeof(BkConjunct) * n_having);
+            return 0;
+        } else if (ty == BK_SCAN_NODE) {
+            if (n_having) {
+                state->error_msg = "HAVING_FILTER_NODE without an aggregate below";
+                return -1;
+            }
+            src->table = static_cast<ScanNode*>(n)->table();
+            if (where) {
+                src->q.n_conjuncts = where->n_conjuncts();
+                memcpy(src->q.conjuncts, where->conjuncts(),
+                       sizeof(src->q.conjuncts));
+            }
+            return 0;
+        }
+    }
+    state->error_msg = "no scan below";
+    return -1;
+}
+
+/* the aggregate whose rows a HAVING root re-emits (null if none below) */
+static AggNode* agg_below(ExecNode* node) {
+    for (ExecNode* n = node; n; n = n->children().empty() ? nullptr : n->children()[0])
+        if (is_agg_node(n)) return static_cast<AggNode*>(n);
+    return nullptr;
+}
+
+int FilterNode::n_slots() {
+    if (_ncols == 0) {
+        if (is_having()) {
+            AggNode* agg = agg_below(this);
+            if (agg) _ncols = agg->n_slots();
+        } else {
+            ScanNode* scan = find_scan(this);
+            if (scan) _ncols = bkgpu_table_ncols(scan->table());
+        }
+    }
+    return _ncols;
+}
+
+int FilterNode::open(RuntimeState* state) {
+    if (is_having()) {
+        /* effective-root HAVING: own conjuncts + those of any HAVING below,
+         * over the aggregate's materialized table */
+        Source source;
+        if (source_of(this, state, &source) < 0) return -1;
+        if (!source.from_agg ||
+            source.q.n_conjuncts + _n_conjuncts > BK_MAX_CONJUNCTS) {
+            state->error_msg = "HAVING_FILTER_NODE: bad plan below";
+            return -1;
+        }
+        _src_q = source.q;
+        for (int i = 0; i < _n_conjuncts; i++)
+            _src_q.conjuncts[_src_q.n_conjuncts++] = _conjuncts[i];
+        _src_table = source.table;
+    }
+    return ExecNode::open(state);
+}
 
 /* ---- SortNode + TopN (sort_node.cpp:278-440, topn_sorter.h:32-63): open()
  * drains the child via the GPU top-N selection, get_next() emits the
@@ -635,24 +809,25 @@ public:
         return 0;
     }
     int open(RuntimeState* state) override {
+        /* source first (an aggregate below is drained as a table there);
+         * above an aggregate, order/out_cols are slot indices, HAVING
+         * conjuncts ride in the top-N query and ties fall in canonical
+         * group order (the materialized table's arrival order) */
+        Source source;
+        if (source_of(this, state, &source) < 0) return -1;
         int ret = ExecNode::open(state);
         if (ret < 0) return ret;
-        ScanNode* scan = find_scan(this);
-        if (!scan) { state->error_msg = "SortNode: no scan below"; return -1; }
-        FilterNode* filter = find_filter(this);
-        BkQuerySpec q{};
-        if (filter) {
-            q.n_conjuncts = filter->n_conjuncts();
-            memcpy(q.conjuncts, filter->conjuncts(), sizeof(q.conjuncts));
-        }
-        BkgTable* t = scan->table();
+        BkQuerySpec q = source.q;
+        BkgTable* t = source.table;
         int64_t limit = _limit > 0 ? _limit : bkgpu_table_nrows(t);
         _rowids.resize(limit > 0 ? limit : 1);
-        int64_t got = bkgpu_sort_topk(t, &q, _desc.order, _desc.n_order, 0,
-                                      bkgpu_table_nrows(t), limit, _rowids.data());
+        int64_t got = 0;
+        if (!(source.from_agg && bkgpu_table_nrows(t) == 0))
+            got = bkgpu_sort_topk(t, &q, _desc.order, _desc.n_order, 0,
+                                  bkgpu_table_nrows(t), limit, _rowids.data());
         if (got < 0) { state->error_msg = bkgpu_last_error(); return -1; }
         _rowids.resize(got);
-        state->inc_num_scan_rows(bkgpu_table_nrows(t));
+        if (!source.from_agg) state->inc_num_scan_rows(bkgpu_table_nrows(t));
         /* materialize out_cols */
         _cols_i.assign(_desc.n_out_cols, {});
         _cols_d.assign(_desc.n_out_cols, {});
@@ -739,33 +914,34 @@ public:
         }
     }
     int open(RuntimeState* state) override {
+        /* source first (see SortNode::open); above an aggregate part_col,
+         * order, fn inputs and out_cols are slot indices */
+        Source source;
+        if (source_of(this, state, &source) < 0) return -1;
         int ret = ExecNode::open(state);
         if (ret < 0) return ret;
-        ScanNode* scan = find_scan(this);
-        if (!scan) { state->error_msg = "WindowNode: no scan below"; return -1; }
-        FilterNode* filter = find_filter(this);
-        BkQuerySpec q{};
-        if (filter) {
-            q.n_conjuncts = filter->n_conjuncts();
-            memcpy(q.conjuncts, filter->conjuncts(), sizeof(q.conjuncts));
-        }
-        BkgTable* t = scan->table();
+        BkQuerySpec q = source.q;
+        BkgTable* t = source.table;
         int64_t nrows = bkgpu_table_nrows(t);
         _rowids.resize(nrows ? nrows : 1);
         _win_i.resize((size_t)_desc.n_winfns * (nrows ? nrows : 1));
         _win_d.resize((size_t)_desc.n_winfns * (nrows ? nrows : 1));
         _win_n.resize((size_t)_desc.n_winfns * (nrows ? nrows : 1));
-        int64_t got = bkgpu_window(t, &q, _desc.part_col, _desc.order,
-                                   _desc.n_order, _desc.winfns, _desc.n_winfns,
-                                   _desc.frame_mode,
-                                   _desc.frame_mode ? _desc.frame_pre : -1,
-                                   _desc.frame_mode ? _desc.frame_fol : -1,
-                                   0, nrows, _rowids.data(), _win_i.data(),
-                                   _win_d.data(), _win_n.data());
+        int64_t got = 0;
+        if (!(source.from_agg && nrows == 0))
+            got = bkgpu_window(t, &q, _desc.part_col, _desc.order,
+                               _desc.n_order, _desc.winfns, _desc.n_winfns,
+                               _desc.frame_mode,
+                               _desc.frame_mode ? _desc.frame_pre : -1,
+                               _desc.frame_mode ? _desc.frame_fol : -1,
+                               0, nrows, _rowids.data(), _win_i.data(),
+                               _win_d.data(), _win_n.data());
         if (got < 0) { state->error_msg = bkgpu_last_error(); return -1; }
         _n = got;
-        state->inc_num_scan_rows(nrows);
-        state->inc_num_filter_rows(nrows - got);
+        if (!source.from_agg) {
+            state->inc_num_scan_rows(nrows);
+            state->inc_num_filter_rows(nrows - got);
+        }
         _fn_types.resize(_desc.n_winfns);
         for (int f = 0; f < _desc.n_winfns; f++)
             _fn_types[f] = fn_out_type(_desc.winfns[f], t);
@@ -897,7 +1073,10 @@ ExecNode* ExecNode::create_exec_node(const BkPlanNodeDesc& node) {
         case BK_AGG_NODE:
         case BK_MERGE_AGG_NODE:    return new AggNode();
         case BK_TABLE_FILTER_NODE:
-        case BK_WHERE_FILTER_NODE: return new FilterNode();
+        case BK_WHERE_FILTER_NODE:
+        /* HAVING is a FilterNode too (exec_node.cpp:413); its conjuncts
+         * stay above the aggregate (filter_node.cpp:545-550) */
+        case BK_HAVING_FILTER_NODE: return new FilterNode();
         case BK_LIMIT_NODE:        return new LimitNode();
         default:                   return nullptr;
     }
@@ -953,7 +1132,8 @@ static int tree_n_slots(const BkExecTree* t) {
     if (n->node_type() == BK_WINDOW_NODE)
         return static_cast<WindowNode*>(n)->n_slots();
     if (n->node_type() == BK_TABLE_FILTER_NODE ||
-        n->node_type() == BK_WHERE_FILTER_NODE)
+        n->node_type() == BK_WHERE_FILTER_NODE ||
+        n->node_type() == BK_HAVING_FILTER_NODE)   /* slots of the AGG below */
         return static_cast<FilterNode*>(n)->n_slots();
     return 0;
 }

@@ -2535,6 +2535,11 @@ extern "C" int32_t bkgpu_table_col_type(const BkgTable* t, int col) {
     return t->specs[col].col_type;
 }
 
+extern "C" int bkgpu_table_col_nullable(const BkgTable* t, int col) {
+    if (!t || col < 0 || col >= t->ncols) return -1;
+    return t->valid[col] ? 1 : 0;
+}
+
 extern "C" void bkgpu_table_free(BkgTable* t) {
     if (!t) return;
     for (int c = 0; c < t->ncols; c++) {
@@ -4313,3 +4318,4 @@ extern "C" int bkgpu_gather(BkgTable* t, int col, const int64_t* rowids_host,
 #include "bksort.inc"
 #include "bkwin.inc"
 #include "bkdedup.inc"
+#include "bkpost.inc"

@@ -1,0 +1,353 @@
+// bkpost.inc — post-aggregation bridge: a finished aggregate materialized as
+// an HBM-resident BkgTable of FINALIZED values, so HAVING (the filter),
+// ORDER BY/LIMIT (top-N), window functions and re-aggregation run over
+// GROUP BY output with the kernels they already have. Included from
+// bkgpu.hip (shares BkgTable / BkgAggOut / agg_compact / the pool).
+//
+// Source: the compact wire blob (agg_compact) — every result form (hash
+// table, dense arrays, sort-dedup table, scalar slot 0) settles into it, so
+// nothing here is per-form:
+//   [ flags: u32 * c ][ k0: u64 * c ][ k1: u64 * c ][ states: u64 * c*2*naggs ]
+// Finalization restates bkgpu_agg_fetch (agg_fn_call.cpp:927-975) and the
+// key decode of AggNode::get_next (agg_node.cpp:548-573) on the device.
+
+#define POST_MAX_COLS (BK_MAX_GROUP + BK_MAX_AGGS)
+
+/* by-value kernel arguments: walked ONLY with compile-time indices inside
+ * fully unrolled loops (no runtime indexing into kernarg-resident arrays,
+ * DESIGN §4/§6) */
+struct PostKeys {
+    int32_t  bits[BK_MAX_GROUP];      /* declared width, 64 = full word */
+    int32_t  type[BK_MAX_GROUP];      /* OUTPUT column type */
+    uint64_t base_enc[BK_MAX_GROUP];  /* encoding of the declared base */
+};
+struct PostAggs {
+    int32_t agg_type[BK_MAX_AGGS];
+    int32_t in_type[BK_MAX_AGGS];
+};
+struct PostCols {
+    void*    data[POST_MAX_COLS];     /* int32 (BK_STRING) or 8-byte cells */
+    uint8_t* valid[POST_MAX_COLS];    /* null for COUNT-shaped columns */
+};
+
+/* store one finalized cell; returns the wave's "saw a NULL" as a bool */
+__device__ __forceinline__ bool post_store(void* data, uint8_t* valid,
+                                           int32_t type, int64_t i, bool live,
+                                           bool has, uint64_t bits64) {
+    if (live) {
+        if (type == BK_STRING) ((int32_t*)data)[i] = has ? (int32_t)(uint32_t)bits64 : 0;
+        else ((uint64_t*)data)[i] = has ? bits64 : 0;
+        if (valid) valid[i] = has ? 1 : 0;
+    }
+    return __ballot(live && !has) != 0;
+}
+
+/* one thread per OUTPUT row i; reads group g = perm[i] (g = i when perm is
+ * null) and writes every output column coalesced. nullmask: bit c set <=>
+ * column c holds at least one NULL (one atomic per wave). */
+__global__ void __launch_bounds__(256)
+k_agg_finalize(const uint32_t* __restrict__ flags,
+               const uint64_t* __restrict__ k0,
+               const uint64_t* __restrict__ k1,
+               const uint64_t* __restrict__ states,
+               const uint32_t* __restrict__ perm, int64_t n,
+               int n_group, int n_aggs, PostKeys pk, PostAggs pa, PostCols pc,
+               uint32_t* nullmask) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool live = i < n;
+    const int64_t g = live ? (perm ? (int64_t)perm[i] : i) : 0;
+    uint32_t seen = 0;
+    uint32_t flag = 0;
+    uint64_t w0 = 0, w1 = 0;
+    if (live && n_group > 0) { flag = flags[g]; w0 = k0[g]; w1 = k1[g]; }
+
+    /* group keys: unpack_group_keys restated (spec widths + bases, null bit
+     * flags >> (7-k)), decoded as AggNode::get_next does */
+    int shift = 0, word = 0;
+    #pragma unroll
+    for (int k = 0; k < BK_MAX_GROUP; k++) {
+        if (k < n_group) {
+            const int bits = pk.bits[k];
+            if (shift + bits > 64) { word++; shift = 0; }
+            const uint64_t w = word == 0 ? w0 : w1;
+            const bool has = !((flag >> (7 - k)) & 1);
+            uint64_t e;
+            if (bits == 64) e = w >> shift;   /* shift is 0 for a full word */
+            else e = ((w >> shift) & ((1ull << bits) - 1)) + pk.base_enc[k];
+            shift += bits;
+            const int32_t ty = pk.type[k];
+            uint64_t out;
+            if (ty == BK_DOUBLE) {
+                double d = bk_dec_f64(e);
+                __builtin_memcpy(&out, &d, 8);
+            } else if (ty == BK_STRING) {
+                out = (uint64_t)(uint32_t)e;
+            } else {
+                out = (uint64_t)bk_dec_i64(e);
+            }
+            if (post_store(pc.data[k], pc.valid[k], ty, i, live, has, out))
+                seen |= 1u << k;
+        }
+    }
+
+    /* aggregates: the finalize switch of bkgpu_agg_fetch restated */
+    #pragma unroll
+    for (int a = 0; a < BK_MAX_AGGS; a++) {
+        if (a < n_aggs) {
+            uint64_t val = 0, cnt = 0;
+            if (live) {
+                const uint64_t* s = states + ((uint64_t)g * 2 * (uint64_t)n_aggs
+                                              + 2 * (uint64_t)a);
+                val = s[0];
+                cnt = s[1];
+            }
+            const int at = pa.agg_type[a];
+            const int vt = pa.in_type[a];
+            bool has = false;
+            uint64_t out = 0;
+            int32_t ty = BK_INT64;
+            switch (at) {
+                case BK_AGG_COUNT_STAR:
+                case BK_AGG_COUNT:
+                case BK_AGG_COUNT_DISTINCT:  /* COUNT-shaped state */
+                    out = val; has = true; break;
+                case BK_AGG_SUM_DISTINCT:    /* SUM-shaped state */
+                case BK_AGG_SUM:
+                    ty = vt;
+                    if (!cnt) break;
+                    out = val; has = true; break;
+                case BK_AGG_AVG:
+                case BK_AGG_AVG_DISTINCT: {
+                    ty = BK_DOUBLE;
+                    if (!cnt) break;
+                    /* one IEEE f64 division, bit-identical to the host's */
+                    double s;
+                    __builtin_memcpy(&s, &val, 8);
+                    double q = s / (double)cnt;
+                    __builtin_memcpy(&out, &q, 8);
+                    has = true; break;
+                }
+                case BK_AGG_MIN:
+                case BK_AGG_MAX: {
+                    ty = vt;
+                    if (!cnt) break;
+                    uint64_t e = (at == BK_AGG_MIN) ? ~val : val;
+                    if (vt == BK_DOUBLE) {
+                        double d = bk_dec_f64(e);
+                        __builtin_memcpy(&out, &d, 8);
+                    } else if (vt == BK_STRING) {
+                        out = (uint64_t)(uint32_t)e;
+                    } else {
+                        out = (uint64_t)bk_dec_i64(e);
+                    }
+                    has = true; break;
+                }
+                default: break;
+            }
+            if (post_store(pc.data[BK_MAX_GROUP + a], pc.valid[BK_MAX_GROUP + a],
+                           ty, i, live, has, out))
+                seen |= 1u << (BK_MAX_GROUP + a);
+        }
+    }
+    if ((threadIdx.x & 63) == 0 && seen) atomicOr(nullmask, seen);
+}
+
+/* sort key of one canonical-order pass for output position i (group
+ * perm[i], or i on the first pass): the key's packed field — order-
+ * preserving within one key because every group shares the base — with
+ * NULL keys as 0; nullbit < 0 selects the flag byte instead. */
+__global__ void __launch_bounds__(256)
+k_post_sortkey(const uint32_t* __restrict__ flags,
+               const uint64_t* __restrict__ kw, const uint32_t* __restrict__ perm,
+               int64_t n, int shift, uint64_t mask, int nullbit,
+               uint64_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int64_t g = perm ? (int64_t)perm[i] : i;
+    const uint32_t f = flags[g];
+    if (nullbit < 0) { out[i] = f & 0xffu; return; }
+    out[i] = ((f >> nullbit) & 1) ? 0 : ((kw[g] >> shift) & mask);
+}
+
+/* canonical MutTableKey order of the blob's groups as a device permutation
+ * (the comparator of bkgpu_agg_fetch: flags first, then each non-NULL key's
+ * encoding in key order): stable LSD radix passes from the last key to the
+ * first, then the flag byte. Returns a pool buffer (caller frees) or null. */
+static uint32_t* post_canonical_perm(const BkgAggOut* o, double* t_ms) {
+    const BkQuerySpec& q = o->q;
+    const int64_t n = o->ngroups, c = o->blob_groups;
+    const uint8_t* b = o->blob;
+    const uint32_t* flags = (const uint32_t*)b;
+    const uint64_t* kw[2] = {(const uint64_t*)(b + c * 4),
+                             (const uint64_t*)(b + c * 12)};
+    /* key layout: the pack_group_keys walk */
+    int kshift[BK_MAX_GROUP], kword[BK_MAX_GROUP], kbits[BK_MAX_GROUP];
+    int shift = 0, word = 0;
+    for (int k = 0; k < q.n_group; k++) {
+        int bits = q.group_bits[k] ? q.group_bits[k] : 64;
+        if (shift + bits > 64) { word++; shift = 0; }
+        kshift[k] = shift; kword[k] = word; kbits[k] = bits;
+        shift += bits;
+    }
+    uint32_t *pa = nullptr, *pb = nullptr;
+    uint64_t *keys = nullptr, *keys_out = nullptr;
+    void* rp_tmp = nullptr;
+    size_t rp_bytes = 0;
+    (void)rocprim::radix_sort_pairs(nullptr, rp_bytes, (uint64_t*)nullptr,
+                                    (uint64_t*)nullptr, (uint32_t*)nullptr,
+                                    (uint32_t*)nullptr, (size_t)n, 0, 64);
+    bool ok = pool_alloc((void**)&pa, (size_t)n * 4) == hipSuccess &&
+              pool_alloc((void**)&pb, (size_t)n * 4) == hipSuccess &&
+              pool_alloc((void**)&keys, (size_t)n * 8) == hipSuccess &&
+              pool_alloc((void**)&keys_out, (size_t)n * 8) == hipSuccess &&
+              pool_alloc(&rp_tmp, rp_bytes ? rp_bytes : 1) == hipSuccess;
+    const unsigned blocks = (unsigned)((n + 255) / 256);
+    bool first = true;
+    double t0 = t_ms ? now_ms() : 0;
+    for (int k = q.n_group - 1; ok && k >= -1; k--) {
+        const bool fl = k < 0;
+        const int bits = fl ? 8 : kbits[k];
+        hipLaunchKernelGGL(k_post_sortkey, dim3(blocks), dim3(256), 0, 0,
+                           flags, fl ? kw[0] : kw[kword[k]],
+                           first ? (const uint32_t*)nullptr : pa, n,
+                           fl ? 0 : kshift[k],
+                           bits >= 64 ? ~0ull : (1ull << bits) - 1,
+                           fl ? -1 : 7 - k, keys);
+        if (first)
+            hipLaunchKernelGGL(k_iota, dim3(256), dim3(256), 0, 0, pa,
+                               (uint64_t)n);
+        ok = hipGetLastError() == hipSuccess &&
+             rocprim::radix_sort_pairs(rp_tmp, rp_bytes, keys, keys_out, pa,
+                                       pb, (size_t)n, 0, (unsigned)bits)
+                 == hipSuccess;
+        std::swap(pa, pb);
+        first = false;
+    }
+    if (ok && t_ms) { (void)hipDeviceSynchronize(); *t_ms = now_ms() - t0; }
+    pool_free(pb); pool_free(keys); pool_free(keys_out); pool_free(rp_tmp);
+    if (!ok) {
+        set_err("agg_to_table: canonical sort failed");
+        pool_free(pa);
+        return nullptr;
+    }
+    return pa;
+}
+
+extern "C" BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src,
+                                        int canonical) {
+    if (!o) { set_err("agg_to_table: null aggregate"); return nullptr; }
+    if (ensure_device() != 0) return nullptr;
+    if (agg_compact(o) != 0) return nullptr;
+    const BkQuerySpec& q = o->q;
+    const int64_t n = o->ngroups, c = o->blob_groups;
+    if (n < 0 || n >= (int64_t(1) << 31)) {
+        set_err("agg_to_table: group count out of range (>= 2^31)");
+        return nullptr;
+    }
+    if (q.n_group < 0 || q.n_group > BK_MAX_GROUP || q.n_aggs < 0 ||
+        q.n_aggs > BK_MAX_AGGS || q.n_group + q.n_aggs < 1) {
+        set_err("agg_to_table: bad group/agg counts");
+        return nullptr;
+    }
+    const bool timing = debug_timing();
+    PostKeys pk{};
+    PostAggs pa{};
+    PostCols pc{};
+    BkgTable* t = new BkgTable();
+    t->ncols = q.n_group + q.n_aggs;
+    t->nrows = n;
+    int slot_of[POST_MAX_COLS];      /* table column -> PostCols slot */
+    int src_col[POST_MAX_COLS];      /* dictionary source column, -1 none */
+    for (int k = 0; k < q.n_group; k++) {
+        pk.bits[k] = q.group_bits[k] ? q.group_bits[k] : 64;
+        pk.type[k] = q.group_fns[k] ? BK_INT64 : q.group_types[k];
+        pk.base_enc[k] = q.group_types[k] == BK_STRING
+                             ? (uint64_t)q.group_base[k]
+                             : bk_enc_i64(q.group_base[k]);
+        t->specs[k].col_type = pk.type[k];
+        slot_of[k] = k;
+        src_col[k] = q.group_cols[k];
+    }
+    for (int a = 0; a < q.n_aggs; a++) {
+        const int at = q.aggs[a].agg_type, vt = q.agg_in_types[a];
+        pa.agg_type[a] = at;
+        pa.in_type[a] = vt;
+        int32_t ot;    /* agg_out_type (bkexec.cpp) */
+        switch (at) {
+            case BK_AGG_COUNT_STAR: case BK_AGG_COUNT:
+            case BK_AGG_COUNT_DISTINCT: ot = BK_INT64; break;
+            case BK_AGG_AVG: case BK_AGG_AVG_DISTINCT: ot = BK_DOUBLE; break;
+            default: ot = vt; break;
+        }
+        const int col = q.n_group + a;
+        t->specs[col].col_type = ot;
+        slot_of[col] = BK_MAX_GROUP + a;
+        src_col[col] = ((at == BK_AGG_MIN || at == BK_AGG_MAX) &&
+                        q.aggs[a].prog_len == 0) ? q.aggs[a].col : -1;
+    }
+    uint32_t* d_mask = nullptr;
+    uint32_t* perm = nullptr;
+    uint32_t h_mask = 0;
+    double ms_sort = 0, ms_fin = 0;
+    bool ok = true;
+    for (int col = 0; ok && col < t->ncols; col++) {
+        const size_t es = elem_size(t->specs[col].col_type);
+        if (es == 0) { set_err("agg_to_table: unsupported column type"); ok = false; break; }
+        t->width[col] = (uint8_t)es;
+        /* every table column carries the 16-byte tail pad (cell_i64) */
+        ok = hipMalloc(&t->data[col], (size_t)n * es + 16) == hipSuccess;
+        const bool count_shaped = col >= q.n_group &&
+            (pa.agg_type[col - q.n_group] == BK_AGG_COUNT_STAR ||
+             pa.agg_type[col - q.n_group] == BK_AGG_COUNT ||
+             pa.agg_type[col - q.n_group] == BK_AGG_COUNT_DISTINCT);
+        if (ok && !count_shaped && n > 0)
+            ok = hipMalloc((void**)&t->valid[col], (size_t)n) == hipSuccess;
+        if (!ok) set_err("agg_to_table: hipMalloc column failed");
+        pc.data[slot_of[col]] = t->data[col];
+        pc.valid[slot_of[col]] = t->valid[col];
+    }
+    if (ok && n > 0) {
+        if (canonical && q.n_group > 0 && n > 1) {
+            perm = post_canonical_perm(o, timing ? &ms_sort : nullptr);
+            ok = perm != nullptr;
+        }
+        ok = ok && pool_alloc((void**)&d_mask, 4) == hipSuccess &&
+             hipMemset(d_mask, 0, 4) == hipSuccess;
+        if (ok) {
+            const uint8_t* b = o->blob;
+            double t0 = timing ? now_ms() : 0;
+            hipLaunchKernelGGL(k_agg_finalize, dim3((unsigned)((n + 255) / 256)),
+                               dim3(256), 0, 0,
+                               (const uint32_t*)b, (const uint64_t*)(b + c * 4),
+                               (const uint64_t*)(b + c * 12),
+                               (const uint64_t*)(b + c * 20),
+                               (const uint32_t*)perm, n, (int)q.n_group,
+                               (int)q.n_aggs, pk, pa, pc, d_mask);
+            ok = hipGetLastError() == hipSuccess &&
+                 hipMemcpy(&h_mask, d_mask, 4, hipMemcpyDeviceToHost) == hipSuccess;
+            if (!ok) set_err("agg_to_table: finalize kernel failed");
+            if (timing) ms_fin = now_ms() - t0;
+        }
+    }
+    pool_free(d_mask);
+    pool_free(perm);
+    if (!ok) { bkgpu_table_free(t); return nullptr; }
+    for (int col = 0; col < t->ncols; col++) {
+        /* keep validity only where a NULL was seen: a NULL-free result stays
+         * eligible for the SIMPLE / dense / sort-dedup routes downstream */
+        if ((h_mask >> slot_of[col]) & 1) {
+            t->specs[col].null_frac_x1e6 = 1;
+        } else if (t->valid[col]) {
+            (void)hipFree(t->valid[col]);
+            t->valid[col] = nullptr;
+        }
+        const int sc = src_col[col];
+        if (t->specs[col].col_type == BK_STRING && dict_src && sc >= 0 &&
+            sc < dict_src->ncols && dict_src->dict[sc])
+            t->dict[col] = new std::vector<std::string>(*dict_src->dict[sc]);
+    }
+    if (timing)
+        fprintf(stderr, "[bkgpu] agg_to_table: %lld groups, perm sort %.3f ms, "
+                        "finalize %.3f ms\n", (long long)n, ms_sort, ms_fin);
+    return t;
+}

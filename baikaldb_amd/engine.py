@@ -162,6 +162,12 @@ def _load():
                                     C.POINTER(C.c_int64), C.POINTER(C.c_double),
                                     C.POINTER(C.c_uint8)]
     lib.bkgpu_agg_free.argtypes = [C.c_void_p]
+    lib.bkgpu_agg_to_table.restype = C.c_void_p
+    lib.bkgpu_agg_to_table.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib.bkgpu_table_ncols.restype = C.c_int32
+    lib.bkgpu_table_ncols.argtypes = [C.c_void_p]
+    lib.bkgpu_table_col_nullable.restype = C.c_int
+    lib.bkgpu_table_col_nullable.argtypes = [C.c_void_p, C.c_int]
     lib.bkgpu_sort_topk.restype = C.c_int64
     lib.bkgpu_sort_topk.argtypes = [C.c_void_p, C.POINTER(BkQuerySpec),
                                     C.POINTER(BkOrderSpec), C.c_int,
@@ -286,6 +292,30 @@ class AggResult:
             "agg_has": out_has[:na * got].reshape(na, got) if got else
                        np.zeros((na, 0), np.uint8),
         }
+
+    def to_table(self, canonical=True, dict_src=None):
+        """Materialize the finished aggregate as a device-resident GpuTable
+        of FINALIZED values (bkgpu_agg_to_table): columns
+        [group keys...][agg outputs...], one row per group, in the order of
+        fetch(sorted=True) when canonical. HAVING is then a QueryPlan
+        conjunct, ORDER BY/LIMIT is sort_topk, and window / filter_agg /
+        derive_expr / the gathers work on it unchanged. dict_src: the table
+        the aggregate ran over (string columns copy its dictionary). This
+        result is left unchanged; the caller frees the table."""
+        lib = self.engine.lib
+        h = lib.bkgpu_agg_to_table(self.handle,
+                                   dict_src.handle if dict_src else None,
+                                   1 if canonical else 0)
+        if not h:
+            raise RuntimeError(
+                f"agg_to_table: {lib.bkgpu_last_error().decode()}")
+        ncols = lib.bkgpu_table_ncols(h)
+        types = [lib.bkgpu_table_col_type(h, c) for c in range(ncols)]
+        t = GpuTable(self.engine, h, types, lib.bkgpu_table_nrows(h))
+        # columns that kept a validity array (hold at least one NULL)
+        t.col_nullable = [bool(lib.bkgpu_table_col_nullable(h, c))
+                          for c in range(ncols)]
+        return t
 
     def free(self):
         if self.handle:

@@ -16,6 +16,7 @@ from .plan import (BkQuerySpec, BkConjunct, BkAggSpec, BkOrderSpec,  # noqa
 BK_MAX_COLS = 16
 SCAN, SORT, AGG, MERGE_AGG, TABLE_FILTER, LIMIT, WHERE_FILTER = 1, 2, 4, 5, 6, 11, 12
 WINDOW = 42
+HAVING_FILTER = 13   # plan.proto:24; built as a FilterNode above the aggregate
 
 
 class BkPlanNodeDesc(C.Structure):
@@ -80,8 +81,10 @@ def filter_node(col_types, conjuncts, num_children=1):
     d.node_type, d.num_children = WHERE_FILTER, num_children
     d.limit = -1
     d.n_conjuncts = len(conjuncts)
-    for i, (col, op, lit) in enumerate(conjuncts):
+    for i, cjt in enumerate(conjuncts):
+        col, op, lit = cjt[0], cjt[1], cjt[2]
         cj = d.conjuncts[i]
+        cj.or_group = cjt[3] if len(cjt) > 3 else 0
         if isinstance(col, tuple):   # ("hour", col): pushed-down scalar fn
             from .plan import _FNS
             cj.fn = _FNS[col[0]]
@@ -92,6 +95,16 @@ def filter_node(col_types, conjuncts, num_children=1):
             cj.cmp_type, cj.lit_d = TYPE_DOUBLE, float(lit)
         else:
             cj.cmp_type, cj.lit_i = TYPE_INT64, int(lit)
+    return d
+
+
+def having_node(slot_types, conjuncts, num_children=1, limit=-1):
+    """HAVING_FILTER_NODE above an AGG node: conjunct columns are slot
+    indices into the aggregate's row [group keys...][agg outputs...];
+    slot_types are the BkType tags of those slots."""
+    d = filter_node(slot_types, conjuncts, num_children)
+    d.node_type = HAVING_FILTER
+    d.limit = limit
     return d
 
 

@@ -7,6 +7,9 @@
 // Usage: region_select <file.parquet>
 //   runs  SELECT g, COUNT(*), SUM(v), MIN(w) FROM t WHERE v < 80 GROUP BY g
 //   and   SELECT g, v FROM t ORDER BY v, g LIMIT 5
+//   and (with an output path) the GROUP BY once more with
+//         HAVING COUNT(*) >= 3 ORDER BY SUM(v) DESC LIMIT 3
+//   serialized as Arrow IPC next to the plain GROUP BY result,
 // over the ingested file and prints the result rows. No Python anywhere:
 // this is the product path an embedder links (libbkgpu.so + headers).
 #include <cstdio>
@@ -227,9 +230,12 @@ static int run_distinct(BkgTable* table) {
  * frontend (region.cpp:2905-2918), written here by the from-scratch
  * serializer (include/bk_arrow.h); pyarrow round-trips the file in
  * tests/test_parquet.py. */
-static int run_agg_arrow(BkgTable* table, const char* out_path) {
-    BkPlanNodeDesc plan[3];
-    memset(plan, 0, sizeof plan);
+static int run_plan_arrow(BkgTable* table, const BkPlanNodeDesc* plan,
+                          int n_nodes, const char* label,
+                          const char* out_path);
+
+/* AGG -> WHERE -> SCAN of the GROUP BY above, written at plan[0..3) */
+static void fill_agg_plan(BkPlanNodeDesc* plan, BkgTable* table) {
     plan[0].node_type = BK_AGG_NODE;
     plan[0].num_children = 1;
     plan[0].limit = -1;
@@ -251,8 +257,50 @@ static int run_agg_arrow(BkgTable* table, const char* out_path) {
     plan[2].node_type = BK_SCAN_NODE;
     plan[2].limit = -1;
     plan[2].table = table;
+}
 
-    BkExecTree* t = bkexec_create_tree(plan, 3);
+static int run_agg_arrow(BkgTable* table, const char* out_path) {
+    BkPlanNodeDesc plan[3];
+    memset(plan, 0, sizeof plan);
+    fill_agg_plan(plan, table);
+    return run_plan_arrow(table, plan, 3, "arrow ipc", out_path);
+}
+
+/* SELECT g, COUNT(*) c, SUM(v) s, MIN(w) FROM t WHERE v < 80 GROUP BY g
+ * HAVING c >= 3 ORDER BY s DESC LIMIT 3 — post-aggregation on the device:
+ * the SortNode drains the AggNode as a materialized table of finalized
+ * values (bkgpu_agg_to_table), the HAVING conjunct rides in the top-N
+ * query; conjunct / order / out_cols indices are SLOT indices into
+ * [g, c, s, min(w)]. Serialized through the same Arrow IPC path. */
+static int run_having_order_arrow(BkgTable* table, const char* out_path) {
+    BkPlanNodeDesc plan[5];
+    memset(plan, 0, sizeof plan);
+    plan[0].node_type = BK_SORT_NODE;
+    plan[0].num_children = 1;
+    plan[0].limit = 3;
+    plan[0].n_order = 1;
+    plan[0].order[0] = {2, 0, 0, 0};    /* s desc, NULLs last */
+    plan[0].n_out_cols = 4;
+    for (int c = 0; c < 4; c++) plan[0].out_cols[c] = c;
+    plan[1].node_type = BK_HAVING_FILTER_NODE;
+    plan[1].num_children = 1;
+    plan[1].limit = -1;
+    plan[1].n_conjuncts = 1;
+    plan[1].conjuncts[0].col = 1;       /* slot 1 = COUNT(*) */
+    plan[1].conjuncts[0].op = BK_OP_GE;
+    plan[1].conjuncts[0].cmp_type = BK_INT64;
+    plan[1].conjuncts[0].lit_i = 3;
+    plan[1].conjuncts[0].col2 = -1;
+    fill_agg_plan(plan + 2, table);
+    std::string path = std::string(out_path) + ".having";
+    return run_plan_arrow(table, plan, 5, "having/order-by arrow ipc",
+                          path.c_str());
+}
+
+static int run_plan_arrow(BkgTable* table, const BkPlanNodeDesc* plan,
+                          int n_nodes, const char* label,
+                          const char* out_path) {
+    BkExecTree* t = bkexec_create_tree(plan, n_nodes);
     if (!t) { fprintf(stderr, "create_tree: %s\n", bkgpu_last_error()); return 1; }
     if (bkexec_open(t) < 0) { fprintf(stderr, "open failed\n"); return 1; }
     int ns = bkexec_n_slots(t);
@@ -336,7 +384,7 @@ static int run_agg_arrow(BkgTable* table, const char* out_path) {
     fwrite(buf, 1, (size_t)blen, f);
     fclose(f);
     bk_arrow_free(buf);
-    printf("arrow ipc: %lld rows, %lld bytes -> %s\n", (long long)nrows,
+    printf("%s: %lld rows, %lld bytes -> %s\n", label, (long long)nrows,
            (long long)blen, out_path);
     bkexec_close(t);
     return 0;
@@ -363,6 +411,7 @@ int main(int argc, char** argv) {
     if (rc == 0) rc = run_window(table);
     if (rc == 0) rc = run_distinct(table);
     if (rc == 0 && argc == 3) rc = run_agg_arrow(table, argv[2]);
+    if (rc == 0 && argc == 3) rc = run_having_order_arrow(table, argv[2]);
     bkgpu_table_free(table);
     return rc;
 }

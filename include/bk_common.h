@@ -38,7 +38,7 @@ typedef enum BkType {
                                 include/common/datetime.h:35-68) */
 } BkType;
 
-/* ---- pb::PlanNodeType subset (proto/plan.proto:10-23) ---- */
+/* ---- pb::PlanNodeType subset (proto/plan.proto:10-24) ---- */
 typedef enum BkNodeType {
     BK_SCAN_NODE         = 1,
     BK_SORT_NODE         = 2,
@@ -47,6 +47,8 @@ typedef enum BkNodeType {
     BK_TABLE_FILTER_NODE = 6,
     BK_LIMIT_NODE        = 11,
     BK_WHERE_FILTER_NODE = 12,
+    BK_HAVING_FILTER_NODE = 13,  /* plan.proto:24; a FilterNode whose conjuncts
+                                    address the aggregate's output slots */
     BK_WINDOW_NODE       = 42,
 } BkNodeType;
 

@@ -40,7 +40,11 @@ typedef struct BkPlanNodeDesc {
                               (limit_node.h:21-41 _offset semantics) */
     /* SCAN_NODE payload */
     BkgTable* table;       /* the region's columnar source */
-    /* WHERE/TABLE_FILTER_NODE payload */
+    /* WHERE/TABLE/HAVING_FILTER_NODE payload. Above an AGG/MERGE_AGG node
+     * every column index of a node — BkConjunct.col/col2, BkOrderSpec.col,
+     * out_cols[], BkWindowFn.col, part_col, group_cols[], BkAggSpec.col —
+     * is a SLOT index into the aggregate's row
+     * [group keys...][agg outputs...]. */
     int32_t    n_conjuncts;
     BkConjunct conjuncts[BK_MAX_CONJUNCTS];
     /* AGG/MERGE_AGG payload */
@@ -92,6 +96,15 @@ int bkexec_open(BkExecTree* t);
  * null flag). Slot layout per root node type:
  *   AGG root:  [group cols...][agg outputs...]
  *   SORT root: [out_cols...]
+ *   HAVING root: the slots and type tags of the AGG below, rows in
+ *              canonical group order
+ * Post-aggregation plans ([LIMIT ->] stands for an optional LIMIT node):
+ *   [LIMIT ->] SORT -> [HAVING ->] AGG -> [WHERE ->] SCAN   (top-N over the
+ *              groups; ties fall in canonical group order)
+ *   [LIMIT ->] HAVING -> AGG -> ...
+ *   WINDOW -> [HAVING ->] AGG -> ...  and  AGG -> [HAVING ->] AGG -> ...
+ * The node above drains the aggregate as a device-resident table
+ * (bkgpu_agg_to_table); NULL HAVING operands reject the group.
  * Writes row-major into out_tag/out_i/out_d/out_null (capacity*n_slots).
  * Returns rows produced (>=0) and sets *eos, or <0 on error. */
 int64_t bkexec_get_next(BkExecTree* t, int64_t capacity, int32_t* out_tag,
@@ -100,7 +113,9 @@ int64_t bkexec_get_next(BkExecTree* t, int64_t capacity, int32_t* out_tag,
 
 int bkexec_n_slots(const BkExecTree* t);
 
-/* RuntimeState counters the store reports back (runtime_state.h:237-270) */
+/* RuntimeState counters the store reports back (runtime_state.h:237-270).
+ * Nodes above an aggregate leave them as the inner AggNode set them:
+ * HAVING-rejected groups are not scan rows or filter rows. */
 int64_t bkexec_num_scan_rows(const BkExecTree* t);
 int64_t bkexec_num_filter_rows(const BkExecTree* t);
 int64_t bkexec_num_rows_returned(const BkExecTree* t);

@@ -95,6 +95,9 @@ int bkgpu_table_derive_remap(BkgTable* t, int src_col, const int32_t* remap,
 int bkgpu_table_derive_prog(BkgTable* t, const BkExprOp* prog, int32_t len,
                             int32_t out_type);
 int32_t bkgpu_table_col_type(const BkgTable* t, int col);
+/* 1 if the column carries a validity array (may hold NULLs), 0 if every
+ * row is valid by construction, <0 on a bad column (introspection). */
+int bkgpu_table_col_nullable(const BkgTable* t, int col);
 int32_t bkgpu_table_ncols(const BkgTable* t);
 void bkgpu_table_free(BkgTable* t);
 
@@ -193,6 +196,17 @@ int64_t bkgpu_agg_fetch(BkgAggOut* o, int sorted, int64_t max_groups,
                         uint8_t* flags, uint64_t* enc,
                         int64_t* out_i, double* out_d, uint8_t* out_has);
 void bkgpu_agg_free(BkgAggOut* o);
+
+/* ---- post-aggregation: HAVING / ORDER BY / window / re-aggregation over
+ * GROUP BY output run on the table this returns ---- */
+/* Materialize a finished aggregate as an HBM-resident table of FINALIZED
+ * values: columns [group key 0..n_group) [agg 0..n_aggs), one row per group.
+ * canonical != 0: rows in the canonical MutTableKey order, i.e. exactly the
+ * order of bkgpu_agg_fetch(sorted=1). dict_src (may be NULL): the table the
+ * aggregate ran over; BK_STRING key / MIN / MAX columns copy its dictionary.
+ * The result is an ordinary BkgTable (free with bkgpu_table_free); `o` stays
+ * valid and unchanged. NULL on error. */
+BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src, int canonical);
 
 /* ---- ORDER BY ... LIMIT top-N ----
  * Select the `limit` smallest rows of [row_begin,row_end) passing q's filter
