@@ -589,25 +589,15 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
                                               int64_t row_begin,
                                               int64_t row_end) {
     if (!t || !q || q->n_group < 1) { set_err("sorted: need GROUP BY"); return nullptr; }
-    if (query_exprs_check(t, q) != 0) return nullptr;
+    if (query_shape_check(t, q) != 0) return nullptr;
     SortPack sp{};
     int bits_total = 0;
-    bool declared = true;
-    for (int32_t k = 0; k < q->n_group; k++) {
-        int b = q->group_bits[k] ? q->group_bits[k] : 64;
-        if (q->group_bits[k] &&
-            (q->group_bits[k] < 0 || q->group_bits[k] > 63 ||
-             q->group_types[k] == BK_DOUBLE)) {
-            set_err("bad group_bits (1..63; DOUBLE keys need bits==0)");
-            return nullptr;
-        }
-        bits_total += b;
-    }
+    for (int32_t k = 0; k < q->n_group; k++)
+        bits_total += q->group_bits[k] ? q->group_bits[k] : 64;
     if (bits_total > 56) {
         /* no usable declared widths: AUTO-pack from column stats (per-key
          * encoding span; works for INT64/DATETIME/DOUBLE/dict encodings
          * alike since only exact encodings are reconstructed at emit) */
-        declared = false;
         if (q->n_group > 2) {
             set_err("sorted: auto-pack supports <= 2 group keys");
             return nullptr;
@@ -634,7 +624,6 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
             return nullptr;
         }
     }
-    (void)declared;
     int64_t range = row_end - row_begin;
     if (range <= 0) { set_err("sorted: empty range"); return nullptr; }
     if (range >= (int64_t)UINT32_MAX) {

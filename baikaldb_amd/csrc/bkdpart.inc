@@ -1303,14 +1303,8 @@ static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
     if (const char* e = getenv("BK_DPIPE")) npipe = atoi(e);
     if (npipe < 1) npipe = 1;
     if (npipe > 4) npipe = 4;
-    static hipStream_t dstreams[2] = {nullptr, nullptr};
-    if (npipe > 1 && !dstreams[0]) {
-        if (hipStreamCreate(&dstreams[0]) != hipSuccess ||
-            hipStreamCreate(&dstreams[1]) != hipSuccess) {
-            set_err("dense stream create failed");
-            return -1;
-        }
-    }
+    hipStream_t* dstreams = nullptr;
+    if (npipe > 1 && !(dstreams = pipe_streams())) return -1;
 
     const uint32_t P = ds.P;
     const uint32_t nch = (nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK;

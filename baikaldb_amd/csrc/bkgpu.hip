@@ -39,7 +39,9 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <chrono>
 #include <map>
+#include <mutex>
 
 #include "../../include/bk_common.h"
 #include "../../include/bk_datagen.h"
@@ -2389,8 +2391,6 @@ extern "C" int bkgpu_table_dict_word(const BkgTable* t, int col, int64_t code,
  * of an 18 GB record buffer costs ~100s of ms, so cache freed buffers by
  * exact size. Host driving is single-threaded (one bthread drives the exec
  * tree in the reference too — SURVEY §8b threading contract). ---- */
-#include <map>
-#include <mutex>
 static std::multimap<size_t, void*> g_pool_free;
 static std::map<void*, size_t> g_pool_sizes;
 /* a store drives MANY region queries concurrently (different exec trees on
@@ -2426,7 +2426,7 @@ static hipError_t pool_alloc(void** p, size_t bytes) {
  * (hipStreamCreate default) AND callers synchronize a stream (or an event
  * recorded after the last consumer, EvTimer::finish) before freeing
  * buffers a kernel on that stream still references — run_dense /
- * run_partitioned_pipe do exactly that before recycling per-chunk slots.
+ * run_partitioned do exactly that before recycling per-chunk slots.
  * Switching to hipStreamNonBlocking or a stream-ordered allocator would
  * turn this reuse into a device use-after-free; make the pool
  * stream-aware first. */
@@ -3029,30 +3029,34 @@ struct EvTimer {
     }
 };
 
-/* partitioned pipeline for one attempt; returns 0 ok (err flag still to be
- * checked by caller), -1 hard error. */
-#include <sys/time.h>
-static bool debug_timing();
+static bool debug_timing() {
+    static const bool on = getenv("BK_DEBUG") != nullptr;
+    return on;
+}
 static double now_ms() {
-    struct timeval tv;
-    gettimeofday(&tv, nullptr);
-    return tv.tv_sec * 1e3 + tv.tv_usec * 1e-3;
+    using namespace std::chrono;
+    return duration<double, std::milli>(
+        steady_clock::now().time_since_epoch()).count();
 }
 
-/* host-side instantiation pick for histo/scatter: HOT only when the
- * adaptive lock-on is enabled (BK_HOT_MIN <= 4096); default is the lean
- * no-table variant. */
-typedef void (*HistoFn)(DevCols, BkQuerySpec, int64_t, int64_t, uint32_t,
-                        uint16_t*, uint32_t*, uint64_t*, uint64_t, uint64_t,
-                        uint64_t*, uint64_t*, uint32_t*, uint32_t, uint32_t,
-                        uint32_t, uint32_t);
-typedef void (*ScatFn)(DevCols, BkQuerySpec, RecLayout, int64_t, int64_t,
-                       uint32_t, const uint16_t*, const uint32_t*, uint64_t*,
-                       uint64_t, int);
-/* SIMPLE shape: plain int compares on non-nullable columns, no fns/IN/
- * doubles, <= 4 conjuncts, <= 2 fn-free non-nullable group keys — the
- * sysbench/BASELINE shapes. The SIMPLE instantiations compile the unused
- * branches out of the per-row machinery. */
+/* the two streams the chunked pipelines (run_dense, run_partitioned)
+ * alternate between; created once, blocking w.r.t. the null stream (the
+ * pool's reuse invariant, see pool_free). nullptr with bkgpu_last_error()
+ * set when creation failed. */
+static hipStream_t* pipe_streams() {
+    struct Pair {
+        hipStream_t s[2] = {nullptr, nullptr};
+        bool ok;
+        Pair() {
+            ok = hipStreamCreate(&s[0]) == hipSuccess &&
+                 hipStreamCreate(&s[1]) == hipSuccess;
+        }
+    };
+    static Pair p;
+    if (!p.ok) { set_err("pipeline stream create failed"); return nullptr; }
+    return p.s;
+}
+
 /* expression validation of a query spec, run by every entry point that
  * hands the spec to a row_passes / agg_input kernel, before any device
  * work: every program slot passes prog_check, and the legacy single-arith
@@ -3094,6 +3098,44 @@ static int query_exprs_check(const BkgTable* t, const BkQuerySpec* q) {
     return 0;
 }
 
+/* what both level-1 entry points (bkgpu_filter_agg, bkgpu_filter_agg_sorted)
+ * refuse before any device work. Returns 0, or -1 with bkgpu_last_error()
+ * set. */
+static int query_shape_check(const BkgTable* t, const BkQuerySpec* q) {
+    if (!t || !q) { set_err("null table or query spec"); return -1; }
+    if (pack_key_words(q) > 2) {
+        set_err("group keys exceed two packed 64-bit words "
+                "(set group_bits per key, bk_common.h)");
+        return -1;
+    }
+    for (int32_t k = 0; k < q->n_group; k++)
+        if (q->group_bits[k] &&
+            (q->group_bits[k] < 0 || q->group_bits[k] > 63 ||
+             q->group_types[k] == BK_DOUBLE)) {
+            set_err("bad group_bits (1..63; DOUBLE keys need bits==0)");
+            return -1;
+        }
+    for (int32_t k = 0; k < q->n_group; k++)
+        if (q->group_fns[k] && q->group_types[k] != BK_INT64 &&
+            q->group_types[k] != BK_DATETIME) {
+            set_err("group_fns need an int64/DATETIME key column");
+            return -1;
+        }
+    for (int32_t j = 0; j < q->n_conjuncts; j++)
+        if (q->conjuncts[j].or_group < 0 || q->conjuncts[j].or_group > 31) {
+            /* kernels and oracle fold clause ids with & 31 — ids
+             * congruent mod 32 would silently merge into one clause */
+            set_err("or_group out of range (0..31)");
+            return -1;
+        }
+    /* postfix programs + legacy arith slots */
+    return query_exprs_check(t, q);
+}
+
+/* SIMPLE shape: plain int compares on non-nullable columns, no fns/IN/
+ * doubles, <= 4 conjuncts, <= 2 fn-free non-nullable group keys — the
+ * sysbench/BASELINE shapes. The SIMPLE instantiations compile the unused
+ * branches out of the per-row machinery. */
 static bool query_simple(const BkgTable* t, const BkQuerySpec* q) {
     if (q->n_conjuncts > 4 || q->n_group > 2) return false;
     for (int32_t j = 0; j < q->n_conjuncts; j++) {
@@ -3137,6 +3179,20 @@ static BkQuerySpec pad_simple_q(const BkQuerySpec* q) {
     return o;
 }
 
+/* host-side instantiation picks for the hash partition's kernels; a thread
+ * count that has no instantiation falls to 256. HOT only when the adaptive
+ * lock-on is enabled (BK_HOT_MIN <= 4096); default is the lean no-table
+ * variant. */
+typedef void (*HistoFn)(DevCols, BkQuerySpec, int64_t, int64_t, uint32_t,
+                        uint16_t*, uint32_t*, uint64_t*, uint64_t, uint64_t,
+                        uint64_t*, uint64_t*, uint32_t*, uint32_t, uint32_t,
+                        uint32_t, uint32_t);
+typedef void (*ScatFn)(DevCols, BkQuerySpec, RecLayout, int64_t, int64_t,
+                       uint32_t, const uint16_t*, const uint32_t*, uint64_t*,
+                       uint64_t, int);
+typedef void (*PartAggFn)(BkQuerySpec, RecLayout, const uint64_t*, uint64_t,
+                          uint64_t, uint64_t*, uint64_t, uint64_t, uint64_t*,
+                          uint32_t*, uint32_t);
 static HistoFn pick_histo(int threads, bool hot, bool simple) {
     if (simple && !hot) {
         if (threads == 512)  return k_part_histo<512, false, true>;
@@ -3157,83 +3213,68 @@ static ScatFn pick_scat(int threads, bool simple) {
     if (threads == 1024) return k_part_scatter<1024>;
     return k_part_scatter<256>;
 }
+static PartAggFn pick_part_agg(int threads, int ilp) {
+    if (threads == 512)
+        return ilp == 2 ? k_part_agg<512, 2> : k_part_agg<512, 1>;
+    if (threads == 1024)
+        return ilp == 2 ? k_part_agg<1024, 2> : k_part_agg<1024, 1>;
+    return ilp == 2 ? k_part_agg<256, 2> : k_part_agg<256, 1>;
+}
 
 #include "bkdpart.inc"
 
-/* pipelined variant of run_partitioned: the row range splits into chunks
- * and consecutive chunks run on TWO HIP streams, so one chunk's part_agg
- * (LDS-latency-bound, ~1.2 TB/s — NOT HBM-saturated) overlaps the next
- * chunk's histo/scatter (HBM-bound). The global table is shared — its claim
- * protocol is already additive/concurrent (same as inter-block claims), so
- * results are identical to the single-pass run. Per-slot buffers are reused
- * only after their stream synchronizes (the pool is not stream-aware). */
-static int run_partitioned_pipe(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
-                                int64_t row_begin, int64_t row_end,
-                                int64_t expected_groups, int nchunks);
-
-static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
-                           int64_t row_begin, int64_t row_end,
-                           int64_t expected_groups) {
-    {
-        /* two-stream chunk pipelining overlaps one chunk's LDS-latency-
-         * bound part_agg with the next chunk's HBM-bound histo/scatter
-         * (measured -1.8 ms on the 1e9-row config-3 shape; smaller ranges
-         * don't amortize the extra chunk boundaries). BK_PIPE overrides
-         * (0/1 = off, N = chunk count). */
-        int pipe = (row_end - row_begin >= 400 * 1000 * 1000 &&
-                    expected_groups >= (1 << 20)) ? 2 : 0;
-        if (const char* e = getenv("BK_PIPE")) pipe = atoi(e);
-        if (pipe > 1 && row_end - row_begin >= 4 * pipe)
-            return run_partitioned_pipe(o, t, q, row_begin, row_end,
-                                        expected_groups, pipe);
-    }
-    const int stride = SLOT_HDR + 2 * q->n_aggs;
-    int64_t range = row_end - row_begin;
-    if (range >= (int64_t)UINT32_MAX) { set_err("range too large for one pass"); return -1; }
+/* launch plan of the hash-partitioned GROUP BY route (run_partitioned):
+ * kernel instantiations, grids and LDS sizes, fixed once per call. Every
+ * knob of the route is read in part_plan and nowhere else. */
+struct PartPlan {
+    uint32_t P;                 /* hash buckets (a power of two) */
+    int nblocks, threads;       /* histo + scatter grid and block shape */
+    uint32_t nch;               /* OFFS_CHUNK tiles of the per-block counts */
     RecLayout lay;
-    build_rec_layout(t, q, &lay);
-    uint32_t P = 64;
-    while ((int64_t)P < expected_groups / 1024 && P < 4096) P <<= 1;
-    const char* envP = getenv("BK_PART_P");
-    if (envP) P = (uint32_t)atoi(envP);
+    bool simple;
+    BkQuerySpec qpad;
+    const BkQuerySpec* qk;      /* SIMPLE kernels get the padded copy (points
+                                 * into this plan: plans are not copied) */
+    HistoFn histo_fn;
+    ScatFn scat_fn;
+    uint32_t hot_slots, hot_cap, hot_probe, hot_min;
+    size_t histo_lds;
+    bool pair;                  /* BK_PAIR: pair-staged scatter */
+    PartAggFn agg_fn;
+    int at;                     /* part_agg block size */
+    uint32_t agg_lds_slots;
+    size_t agg_lds_bytes;
+    uint64_t agg_chunk;         /* records per part_agg chunk; 0 = sized from
+                                 * the record count */
+    int pipe;                   /* BK_PIPE: 0/1 = single pass, N = chunk
+                                 * count, -1 = unset (decided by size) */
+    uint64_t pipe_agg_grid;     /* part_agg grid cap of the two-stream form */
+    PartPlan() = default;
+    PartPlan(const PartPlan&) = delete;
+};
+
+static void part_plan(PartPlan* pl, BkgTable* t, const BkQuerySpec* q,
+                      int64_t expected_groups) {
+    const int stride = SLOT_HDR + 2 * q->n_aggs;
+    build_rec_layout(t, q, &pl->lay);
+    pl->P = 64;
+    while ((int64_t)pl->P < expected_groups / 1024 && pl->P < 4096) pl->P <<= 1;
+    if (const char* e = getenv("BK_PART_P")) pl->P = (uint32_t)atoi(e);
     /* 8192 blocks: with 3-4 resident blocks/CU the deeper dispatch queue
      * keeps CUs fed through the drain tail (-2-3% on histo+scatter at 1e9;
      * all three kernels are ~70-87% wave-parked on memory waits, so more
      * in-flight blocks are the only free-lunch lever left) */
-    int nblocks = 8192;
-    const char* envB = getenv("BK_PART_BLOCKS");
-    if (envB) nblocks = atoi(envB);
+    pl->nblocks = 8192;
+    if (const char* e = getenv("BK_PART_BLOCKS")) pl->nblocks = atoi(e);
+    pl->nch = (uint32_t)((pl->nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK);
     /* histo+scatter MUST share grid AND block shape (H rows are per-block).
      * 512 threads measured best (histo 5.7->3.4 ms, scatter 9.9->8.3 ms at
      * 3e8 rows): 8 waves/block hides more gather latency; 1024 regresses
      * histo (register cap). */
-    int threads = 512;
-    if (const char* e = getenv("BK_PART_THREADS")) threads = atoi(e);
-    if (threads != 512 && threads != 1024) threads = 256;
-    DevCols dc = table_cols(t);
+    pl->threads = 512;
+    if (const char* e = getenv("BK_PART_THREADS")) pl->threads = atoi(e);
+    if (pl->threads != 512 && pl->threads != 1024) pl->threads = 256;
 
-    uint16_t* bucketid = nullptr;
-    uint32_t *H = nullptr, *totals = nullptr, *base = nullptr, *S = nullptr;
-    uint64_t* total_dev = nullptr;
-    uint64_t* rec = nullptr;
-    auto cleanup = [&]() {
-        pool_free(bucketid); pool_free(H); pool_free(totals); pool_free(base);
-        pool_free(S); pool_free(total_dev); pool_free(rec);
-    };
-    #define PCHECK(x) do { if ((x) != hipSuccess) { \
-        snprintf(g_err, sizeof g_err, "%s:%d %s", __FILE__, __LINE__, \
-                 hipGetErrorString(hipGetLastError())); cleanup(); return -1; } } while (0)
-    const uint32_t nchunks = (nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK;
-    PCHECK(pool_alloc((void**)&bucketid, (size_t)range * 2));
-    PCHECK(pool_alloc((void**)&H, (size_t)nblocks * P * 4));
-    PCHECK(pool_alloc((void**)&totals, (size_t)P * 4));
-    PCHECK(hipMemset(totals, 0, (size_t)P * 4));
-    PCHECK(pool_alloc((void**)&base, (size_t)P * 4));
-    PCHECK(pool_alloc((void**)&S, (size_t)nchunks * P * 4));
-    PCHECK(pool_alloc((void**)&total_dev, 8));
-
-    static const char* NAMES[] = {"histo", "totals", "scan", "offsets",
-                                  "scatter", "part_agg"};
     /* hot-table knobs (defaults from the config3/config2 sweeps; see
      * profiles/ and DESIGN.md §6). lcap = keys the first-come table can
      * hold; under octave-shaped key mass every doubling of lcap absorbs
@@ -3241,174 +3282,101 @@ static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
      * costs histo occupancy. */
     size_t hot_lds_cap = 50 * 1024;
     if (const char* e = getenv("BK_HOT_LDS_KB")) hot_lds_cap = (size_t)atoi(e) * 1024;
-    uint32_t hot_slots = 512;
-    if (const char* e = getenv("BK_HOT_SLOTS")) hot_slots = (uint32_t)atoi(e);
-    while ((size_t)hot_slots * stride * 8 > hot_lds_cap) hot_slots >>= 1;
-    uint32_t hot_cap = hot_slots / 2u;
-    if (const char* e = getenv("BK_HOT_CAP")) hot_cap = (uint32_t)atoi(e);
-    if (hot_cap > hot_slots - hot_slots / 8u) hot_cap = hot_slots - hot_slots / 8u;
-    uint32_t hot_probe = 4;
-    if (const char* e = getenv("BK_HOT_PROBE")) hot_probe = (uint32_t)atoi(e);
+    pl->hot_slots = 512;
+    if (const char* e = getenv("BK_HOT_SLOTS")) pl->hot_slots = (uint32_t)atoi(e);
+    while ((size_t)pl->hot_slots * stride * 8 > hot_lds_cap) pl->hot_slots >>= 1;
+    pl->hot_cap = pl->hot_slots / 2u;
+    if (const char* e = getenv("BK_HOT_CAP")) pl->hot_cap = (uint32_t)atoi(e);
+    if (pl->hot_cap > pl->hot_slots - pl->hot_slots / 8u)
+        pl->hot_cap = pl->hot_slots - pl->hot_slots / 8u;
+    pl->hot_probe = 4;
+    if (const char* e = getenv("BK_HOT_PROBE")) pl->hot_probe = (uint32_t)atoi(e);
     /* default NEVER locks on: at 512-thread histo the per-row LDS probe
      * costs more than the absorption saves on BOTH baseline key shapes
      * (Zipf/1e5 with 46% absorbable: 11.9 -> 9.6 ms with the hot path off;
      * zipfoct x dict: auto-disabled anyway). BK_HOT_MIN=<=4096 re-enables
      * the adaptive lock-on for workloads where it wins. */
-    uint32_t hot_min = 4097;
-    if (const char* e = getenv("BK_HOT_MIN")) hot_min = (uint32_t)atoi(e);
-    bool hot = hot_min <= 4096;
-    if (!hot) hot_slots = 0;
-    bool simple = query_simple(t, q) && getenv("BK_NO_SIMPLE") == nullptr;
-    BkQuerySpec qpad;
-    const BkQuerySpec* qk = q;     /* SIMPLE kernels get the padded copy */
-    if (simple) { qpad = pad_simple_q(q); qk = &qpad; }
-    HistoFn histo_fn = pick_histo(threads, hot, simple);
-    ScatFn scat_fn = pick_scat(threads, simple);
-    size_t histo_lds = ((size_t)hot_slots * stride + 4) * 8 + (size_t)P * 4;
-    EvTimer tm;
-    tm.record();
-    hipLaunchKernelGGL(histo_fn, dim3(nblocks), dim3(threads), histo_lds, 0,
-                       dc, *qk, row_begin, row_end, P, bucketid, H,
-                       o->table, o->nslots - 1, (o->nslots * 7) / 8,
-                       o->ctrs, o->ctrs + 1, o->err, hot_slots,
-                       hot_cap, hot_probe, hot_min);
-    tm.record();
-    hipLaunchKernelGGL(k_part_totals, dim3((P * nchunks + 255) / 256), dim3(256),
-                       0, 0, H, nblocks, P, S, totals);
-    tm.record();
-    hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, 0,
-                       totals, P, base, total_dev);
-    tm.record();
-    PCHECK(hipGetLastError());
-    uint64_t total = 0;
-    PCHECK(hipMemcpy(&total, total_dev, 8, hipMemcpyDeviceToHost));
-    if (getenv("BK_DEBUG")) {
-        uint64_t passed = 0;
-        (void)hipMemcpy(&passed, o->ctrs + 1, 8, hipMemcpyDeviceToHost);
-        fprintf(stderr, "[bkgpu] passed=%llu cold_records=%llu hot_absorbed=%.1f%%\n",
-                (unsigned long long)passed, (unsigned long long)total,
-                passed ? 100.0 * (double)(passed - total) / (double)passed : 0.0);
-    }
-    if (total > 0)
-        PCHECK(pool_alloc((void**)&rec, (size_t)total * lay.nwords * 8));
-    hipLaunchKernelGGL(k_part_offsets, dim3((P * nchunks + 255) / 256), dim3(256),
-                       0, 0, H, nblocks, P, base, S);
-    tm.record();
-    if (total > 0) {
-        /* pair staging halves write traffic (45->24 GB measured) but the
-         * 72 KB stash drops occupancy to 2 blocks/CU and the scatter's
-         * gather reads become latency-bound (33->77 ms): net loss. Kept
-         * opt-in (BK_PAIR=1) until an occupancy-neutral variant exists. */
-        size_t pair_lds = (size_t)P * lay.nwords * 8 + (size_t)P * 8;
-        int paired = pair_lds <= 130 * 1024 && getenv("BK_PAIR") != nullptr;
-        size_t sc_lds = paired ? pair_lds : (size_t)P * 8;
-        hipLaunchKernelGGL(scat_fn, dim3(nblocks), dim3(threads),
-                           sc_lds, 0,
-                           dc, *qk, lay, row_begin, row_end, P, bucketid, H,
-                           rec, total, paired);
-    }
-    tm.record();
-    if (total > 0) {
-        uint32_t lds_slots = 2048;
-        size_t lds_cap = 135 * 1024;
-        const char* envL = getenv("BK_AGG_LDS_KB");
-        if (envL) lds_cap = (size_t)atoi(envL) * 1024;
-        while ((size_t)lds_slots * stride * 8 > lds_cap) lds_slots >>= 1;
-        size_t lds_bytes = ((size_t)lds_slots * stride + 1) * 8;
-        /* chunk ~ bucket size: fewer generation flushes (flush traffic ~
-         * chunks x distinct-per-chunk), while >=2048 chunks keep the chip
-         * balanced */
-        uint64_t chunk = std::max<uint64_t>(
-            32768, std::min<uint64_t>(1u << 20, total / 4096));
-        const char* envC = getenv("BK_AGG_CHUNK");
-        if (envC) chunk = (uint64_t)atoll(envC);
-        uint64_t nchunks = (total + chunk - 1) / chunk;
-        uint32_t grid = (uint32_t)std::min<uint64_t>(nchunks, 32768);
-        /* block size: the 135 KB table allows only 1 block/CU, so waves per
-         * BLOCK are the only latency-hiding lever. 1024 (16 waves/CU)
-         * measured 2.4x faster than 256 on both ~1M-group and 1000-group
-         * shapes (see profiles/; LDS-atomic chains dominate this kernel). */
-        int at = 1024;
-        if (const char* e = getenv("BK_AGG_THREADS")) at = atoi(e);
-        int ilp = 2;  /* 2 records/lane: two independent claim chains (-8%) */
-        if (const char* e = getenv("BK_AGG_ILP")) ilp = atoi(e);
-        auto kfn = k_part_agg<256, 1>;
-        if (at == 512) kfn = ilp == 2 ? k_part_agg<512, 2> : k_part_agg<512, 1>;
-        else if (at == 1024) kfn = ilp == 2 ? k_part_agg<1024, 2>
-                                            : k_part_agg<1024, 1>;
-        else { at = 256; if (ilp == 2) kfn = k_part_agg<256, 2>; }
-        hipLaunchKernelGGL(kfn, dim3(grid), dim3(at), lds_bytes, 0,
-                           *q, lay, rec, total, chunk,
-                           o->table, o->nslots - 1, (o->nslots * 7) / 8,
-                           o->ctrs, o->err, lds_slots);
-    }
-    tm.record();
-    PCHECK(hipGetLastError());
-    tm.finish(o, NAMES);
-    /* rows_passed is accumulated by k_part_histo (hot + cold alike) */
-    cleanup();
-    #undef PCHECK
-    return 0;
-}
+    pl->hot_min = 4097;
+    if (const char* e = getenv("BK_HOT_MIN")) pl->hot_min = (uint32_t)atoi(e);
+    const bool hot = pl->hot_min <= 4096;
+    if (!hot) pl->hot_slots = 0;
+    pl->simple = query_simple(t, q) && getenv("BK_NO_SIMPLE") == nullptr;
+    pl->qk = q;
+    if (pl->simple) { pl->qpad = pad_simple_q(q); pl->qk = &pl->qpad; }
+    pl->histo_fn = pick_histo(pl->threads, hot, pl->simple);
+    pl->scat_fn = pick_scat(pl->threads, pl->simple);
+    pl->histo_lds = ((size_t)pl->hot_slots * stride + 4) * 8 + (size_t)pl->P * 4;
+    /* pair staging halves write traffic (45->24 GB measured) but the
+     * 72 KB stash drops occupancy to 2 blocks/CU and the scatter's
+     * gather reads become latency-bound (33->77 ms): net loss. Kept
+     * opt-in (BK_PAIR=1) until an occupancy-neutral variant exists. */
+    pl->pair = getenv("BK_PAIR") != nullptr;
 
-static int run_partitioned_pipe(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
-                                int64_t row_begin, int64_t row_end,
-                                int64_t expected_groups, int nchunks) {
-    const int stride = SLOT_HDR + 2 * q->n_aggs;
-    RecLayout lay;
-    build_rec_layout(t, q, &lay);
-    uint32_t P = 64;
-    while ((int64_t)P < expected_groups / 1024 && P < 4096) P <<= 1;
-    if (const char* e = getenv("BK_PART_P")) P = (uint32_t)atoi(e);
-    int nblocks = 8192;
-    if (const char* e = getenv("BK_PART_BLOCKS")) nblocks = atoi(e);
-    int threads = 512;
-    if (const char* e = getenv("BK_PART_THREADS")) threads = atoi(e);
-    if (threads != 512 && threads != 1024) threads = 256;
-    int at = 1024;
-    if (const char* e = getenv("BK_AGG_THREADS")) at = atoi(e);
-    int ilp = 2;
-    if (const char* e = getenv("BK_AGG_ILP")) ilp = atoi(e);
-    auto agg_fn = k_part_agg<1024, 2>;
-    if (at == 512) agg_fn = ilp == 2 ? k_part_agg<512, 2> : k_part_agg<512, 1>;
-    else if (at == 256) agg_fn = ilp == 2 ? k_part_agg<256, 2> : k_part_agg<256, 1>;
-    else { at = 1024; if (ilp != 2) agg_fn = k_part_agg<1024, 1>; }
-    uint32_t agg_lds_slots = 2048;
+    pl->agg_lds_slots = 2048;
     size_t agg_lds_cap = 135 * 1024;
     if (const char* e = getenv("BK_AGG_LDS_KB")) agg_lds_cap = (size_t)atoi(e) * 1024;
-    while ((size_t)agg_lds_slots * stride * 8 > agg_lds_cap) agg_lds_slots >>= 1;
-    size_t agg_lds_bytes = ((size_t)agg_lds_slots * stride + 1) * 8;
+    while ((size_t)pl->agg_lds_slots * stride * 8 > agg_lds_cap)
+        pl->agg_lds_slots >>= 1;
+    pl->agg_lds_bytes = ((size_t)pl->agg_lds_slots * stride + 1) * 8;
+    pl->agg_chunk = 0;
+    if (const char* e = getenv("BK_AGG_CHUNK")) pl->agg_chunk = (uint64_t)atoll(e);
+    /* block size: the 135 KB table allows only 1 block/CU, so waves per
+     * BLOCK are the only latency-hiding lever. 1024 (16 waves/CU)
+     * measured 2.4x faster than 256 on both ~1M-group and 1000-group
+     * shapes (see profiles/; LDS-atomic chains dominate this kernel). */
+    pl->at = 1024;
+    if (const char* e = getenv("BK_AGG_THREADS")) pl->at = atoi(e);
+    if (pl->at != 512 && pl->at != 1024) pl->at = 256;
+    int ilp = 2;  /* 2 records/lane: two independent claim chains (-8%) */
+    if (const char* e = getenv("BK_AGG_ILP")) ilp = atoi(e);
+    pl->agg_fn = pick_part_agg(pl->at, ilp);
 
-    uint32_t hot_lds_cap = 50 * 1024;
-    if (const char* e = getenv("BK_HOT_LDS_KB")) hot_lds_cap = (uint32_t)atoi(e) * 1024;
-    uint32_t hot_slots = 512;
-    if (const char* e = getenv("BK_HOT_SLOTS")) hot_slots = (uint32_t)atoi(e);
-    while ((size_t)hot_slots * stride * 8 > hot_lds_cap) hot_slots >>= 1;
-    uint32_t hot_cap = hot_slots / 2u, hot_probe = 4, hot_min = 4097;
-    if (const char* e = getenv("BK_HOT_CAP")) hot_cap = (uint32_t)atoi(e);
-    if (hot_cap > hot_slots - hot_slots / 8u) hot_cap = hot_slots - hot_slots / 8u;
-    if (const char* e = getenv("BK_HOT_PROBE")) hot_probe = (uint32_t)atoi(e);
-    if (const char* e = getenv("BK_HOT_MIN")) hot_min = (uint32_t)atoi(e);
-    bool hot = hot_min <= 4096;
-    if (!hot) hot_slots = 0;
-    bool simple = query_simple(t, q) && getenv("BK_NO_SIMPLE") == nullptr;
-    BkQuerySpec qpad;
-    const BkQuerySpec* qk = q;     /* SIMPLE kernels get the padded copy */
-    if (simple) { qpad = pad_simple_q(q); qk = &qpad; }
-    HistoFn histo_fn = pick_histo(threads, hot, simple);
-    ScatFn scat_fn = pick_scat(threads, simple);
-    size_t histo_lds = ((size_t)hot_slots * stride + 4) * 8 + (size_t)P * 4;
-    size_t sc_lds = (size_t)P * 8;
+    /* two-stream chunk pipelining overlaps one chunk's LDS-latency-
+     * bound part_agg with the next chunk's HBM-bound histo/scatter
+     * (measured -1.8 ms on the 1e9-row config-3 shape; smaller ranges
+     * don't amortize the extra chunk boundaries). BK_PIPE overrides
+     * (0/1 = off, N = chunk count). */
+    pl->pipe = -1;
+    if (const char* e = getenv("BK_PIPE")) pl->pipe = std::max(0, atoi(e));
+    /* cap on the two-stream form's part_agg grid, to leave the OTHER
+     * stream's HBM-bound kernels some CUs: part_agg blocks hold 135 KB LDS
+     * (1/CU) and a full grid occupies the whole chip. The default caps
+     * nothing the single pass would not (a tighter cap measured worse,
+     * DESIGN.md). */
+    pl->pipe_agg_grid = 32768;
+    if (const char* e = getenv("BK_PIPE_AGG_GRID")) pl->pipe_agg_grid = (uint64_t)atoll(e);
+}
 
-    static hipStream_t streams[2] = {nullptr, nullptr};
-    if (!streams[0]) {
-        HIP_CHECK(hipStreamCreate(&streams[0]));
-        HIP_CHECK(hipStreamCreate(&streams[1]));
+/* Hash-partitioned GROUP BY for one attempt; returns 0 ok (err flag still
+ * to be checked by caller), -1 hard error. One loop over row chunks, as in
+ * run_dense. Large ranges split into chunks that alternate between TWO HIP
+ * streams, so one chunk's part_agg (LDS-latency-bound, ~1.2 TB/s — NOT
+ * HBM-saturated) overlaps the next chunk's histo/scatter (HBM-bound). The
+ * global table is shared — its claim protocol is already additive/concurrent
+ * (same as inter-block claims), so results are identical to the single pass,
+ * which is the one-chunk case on the null stream with per-kernel event
+ * timing. Per-slot buffers are reused only after their stream synchronizes
+ * (the pool is not stream-aware). */
+static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
+                           int64_t row_begin, int64_t row_end,
+                           int64_t expected_groups) {
+    const int64_t range = row_end - row_begin;
+    PartPlan pl;
+    part_plan(&pl, t, q, expected_groups);
+    int npipe = (range >= 400 * 1000 * 1000 &&
+                 expected_groups >= (1 << 20)) ? 2 : 1;
+    if (pl.pipe >= 0) npipe = pl.pipe;
+    if (npipe < 2 || range < (int64_t)4 * npipe) npipe = 1;
+    const bool piped = npipe > 1;
+    hipStream_t* streams = nullptr;
+    if (piped && !(streams = pipe_streams())) return -1;
+    const int64_t per = (range + npipe - 1) / npipe;
+    if (per >= (int64_t)UINT32_MAX) {
+        set_err("row chunk too large for one pass");
+        return -1;
     }
-    const uint32_t nch = (uint32_t)((nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK);
-    int64_t range = row_end - row_begin;
-    int64_t per = (range + nchunks - 1) / nchunks;
-    if (per >= (int64_t)UINT32_MAX) { set_err("chunk too large"); return -1; }
+    const uint32_t P = pl.P, nch = pl.nch;
+    const int nblocks = pl.nblocks, threads = pl.threads;
 
     struct Slot {
         uint16_t* bucketid = nullptr;
@@ -3423,83 +3391,115 @@ static int run_partitioned_pipe(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
             pool_free(sl[i].rec);
         }
     };
-    #define PPCHECK(x) do { if ((x) != hipSuccess) { \
-        snprintf(g_err, sizeof g_err, "pipe %s:%d %s", __FILE__, __LINE__, \
+    /* the pool is not stream-aware: nothing goes back to it while a kernel
+     * may still write it */
+    #define PCHECK(x) do { if ((x) != hipSuccess) { \
+        snprintf(g_err, sizeof g_err, "part %s:%d %s", __FILE__, __LINE__, \
                  hipGetErrorString(hipGetLastError())); \
         (void)hipDeviceSynchronize(); cleanup(); return -1; } } while (0)
-    for (int i = 0; i < 2; i++) {
-        PPCHECK(pool_alloc((void**)&sl[i].bucketid, (size_t)per * 2));
-        PPCHECK(pool_alloc((void**)&sl[i].H, (size_t)nblocks * P * 4));
-        PPCHECK(pool_alloc((void**)&sl[i].totals, (size_t)P * 4));
-        PPCHECK(pool_alloc((void**)&sl[i].base, (size_t)P * 4));
-        PPCHECK(pool_alloc((void**)&sl[i].S, (size_t)nch * P * 4));
-        PPCHECK(pool_alloc((void**)&sl[i].total_dev, 8));
+    for (int i = 0; i < (piped ? 2 : 1); i++) {
+        PCHECK(pool_alloc((void**)&sl[i].bucketid, (size_t)per * 2));
+        PCHECK(pool_alloc((void**)&sl[i].H, (size_t)nblocks * P * 4));
+        PCHECK(pool_alloc((void**)&sl[i].totals, (size_t)P * 4));
+        PCHECK(pool_alloc((void**)&sl[i].base, (size_t)P * 4));
+        PCHECK(pool_alloc((void**)&sl[i].S, (size_t)nch * P * 4));
+        PCHECK(pool_alloc((void**)&sl[i].total_dev, 8));
     }
     DevCols dc = table_cols(t);
-    PPCHECK(hipDeviceSynchronize());
-    double t0 = now_ms();
-    for (int c = 0; c < nchunks; c++) {
-        int si = c & 1;
-        hipStream_t st = streams[si];
+
+    static const char* NAMES[] = {"histo", "totals", "scan", "offsets",
+                                  "scatter", "part_agg"};
+    EvTimer tm;
+    double t0 = 0;
+    if (piped) { PCHECK(hipDeviceSynchronize()); t0 = now_ms(); }
+    for (int c = 0; c < npipe; c++) {
+        Slot& s = sl[piped ? (c & 1) : 0];
+        hipStream_t st = piped ? streams[c & 1] : 0;
         int64_t cb = row_begin + (int64_t)c * per;
         int64_t ce = cb + per < row_end ? cb + per : row_end;
         if (ce <= cb) break;
         if (c >= 2) {
             /* slot reuse: its previous chunk must be fully done before we
-             * recycle the record buffer (pool is not stream-aware) */
-            PPCHECK(hipStreamSynchronize(st));
-            pool_free(sl[si].rec);
-            sl[si].rec = nullptr;
+             * recycle the record buffer */
+            PCHECK(hipStreamSynchronize(st));
+            pool_free(s.rec);
+            s.rec = nullptr;
         }
-        PPCHECK(hipMemsetAsync(sl[si].totals, 0, (size_t)P * 4, st));
-        hipLaunchKernelGGL(histo_fn, dim3(nblocks), dim3(threads), histo_lds, st,
-                           dc, *qk, cb, ce, P, sl[si].bucketid, sl[si].H,
+        PCHECK(hipMemsetAsync(s.totals, 0, (size_t)P * 4, st));
+        if (!piped) tm.record();
+        hipLaunchKernelGGL(pl.histo_fn, dim3(nblocks), dim3(threads),
+                           pl.histo_lds, st,
+                           dc, *pl.qk, cb, ce, P, s.bucketid, s.H,
                            o->table, o->nslots - 1, (o->nslots * 7) / 8,
-                           o->ctrs, o->ctrs + 1, o->err, hot_slots,
-                           hot_cap, hot_probe, hot_min);
+                           o->ctrs, o->ctrs + 1, o->err, pl.hot_slots,
+                           pl.hot_cap, pl.hot_probe, pl.hot_min);
+        if (!piped) tm.record();
         hipLaunchKernelGGL(k_part_totals, dim3((P * nch + 255) / 256), dim3(256),
-                           0, st, sl[si].H, nblocks, P, sl[si].S, sl[si].totals);
+                           0, st, s.H, nblocks, P, s.S, s.totals);
+        if (!piped) tm.record();
         hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, st,
-                           sl[si].totals, P, sl[si].base, sl[si].total_dev);
-        PPCHECK(hipGetLastError());
+                           s.totals, P, s.base, s.total_dev);
+        if (!piped) tm.record();
+        PCHECK(hipGetLastError());
         uint64_t total = 0;
-        PPCHECK(hipMemcpyAsync(&total, sl[si].total_dev, 8,
-                               hipMemcpyDeviceToHost, st));
-        PPCHECK(hipStreamSynchronize(st));   /* other stream keeps running */
-        hipLaunchKernelGGL(k_part_offsets, dim3((P * nch + 255) / 256), dim3(256),
-                           0, st, sl[si].H, nblocks, P, sl[si].base, sl[si].S);
-        if (total > 0) {
-            PPCHECK(pool_alloc((void**)&sl[si].rec,
-                               (size_t)total * lay.nwords * 8));
-            hipLaunchKernelGGL(scat_fn, dim3(nblocks), dim3(threads), sc_lds, st,
-                               dc, *qk, lay, cb, ce, P, sl[si].bucketid,
-                               sl[si].H, sl[si].rec, total, 0);
-            uint64_t chunk_sz = std::max<uint64_t>(
-                32768, std::min<uint64_t>(1u << 20, total / 4096));
-            if (const char* e = getenv("BK_AGG_CHUNK")) chunk_sz = (uint64_t)atoll(e);
-            uint64_t nrec_chunks = (total + chunk_sz - 1) / chunk_sz;
-            /* cap the aggregate's grid so the OTHER stream's HBM-bound
-             * kernels keep CUs: part_agg blocks hold 135 KB LDS (1/CU) and
-             * a full grid would occupy the whole chip */
-            uint64_t gmax = 32768;
-            if (const char* e = getenv("BK_PIPE_AGG_GRID")) gmax = (uint64_t)atoll(e);
-            uint32_t grid = (uint32_t)std::min<uint64_t>(nrec_chunks, gmax);
-            hipLaunchKernelGGL(agg_fn, dim3(grid), dim3(at), agg_lds_bytes, st,
-                               *q, lay, sl[si].rec, total, chunk_sz,
-                               o->table, o->nslots - 1, (o->nslots * 7) / 8,
-                               o->ctrs, o->err, agg_lds_slots);
+        PCHECK(hipMemcpyAsync(&total, s.total_dev, 8, hipMemcpyDeviceToHost, st));
+        PCHECK(hipStreamSynchronize(st));   /* other stream keeps running */
+        if (!piped && getenv("BK_DEBUG")) {
+            uint64_t passed = 0;
+            (void)hipMemcpy(&passed, o->ctrs + 1, 8, hipMemcpyDeviceToHost);
+            fprintf(stderr, "[bkgpu] passed=%llu cold_records=%llu hot_absorbed=%.1f%%\n",
+                    (unsigned long long)passed, (unsigned long long)total,
+                    passed ? 100.0 * (double)(passed - total) / (double)passed : 0.0);
         }
-        PPCHECK(hipGetLastError());
+        hipLaunchKernelGGL(k_part_offsets, dim3((P * nch + 255) / 256), dim3(256),
+                           0, st, s.H, nblocks, P, s.base, s.S);
+        if (!piped) tm.record();
+        if (total > 0) {
+            PCHECK(pool_alloc((void**)&s.rec, (size_t)total * pl.lay.nwords * 8));
+            /* BK_PAIR is a single-pass experiment (part_plan: the stash
+             * costs the scatter its occupancy, a net loss); the two-stream
+             * form never pairs */
+            size_t pair_lds = (size_t)P * pl.lay.nwords * 8 + (size_t)P * 8;
+            int paired = !piped && pl.pair && pair_lds <= 130 * 1024;
+            size_t sc_lds = paired ? pair_lds : (size_t)P * 8;
+            hipLaunchKernelGGL(pl.scat_fn, dim3(nblocks), dim3(threads), sc_lds,
+                               st, dc, *pl.qk, pl.lay, cb, ce, P, s.bucketid,
+                               s.H, s.rec, total, paired);
+        }
+        if (!piped) tm.record();
+        if (total > 0) {
+            /* chunk ~ bucket size: fewer generation flushes (flush traffic ~
+             * chunks x distinct-per-chunk), while >=2048 chunks keep the chip
+             * balanced */
+            uint64_t chunk = pl.agg_chunk ? pl.agg_chunk
+                : std::max<uint64_t>(32768,
+                                     std::min<uint64_t>(1u << 20, total / 4096));
+            uint64_t nrec_chunks = (total + chunk - 1) / chunk;
+            uint32_t grid = (uint32_t)std::min<uint64_t>(
+                nrec_chunks, piped ? pl.pipe_agg_grid : 32768);
+            hipLaunchKernelGGL(pl.agg_fn, dim3(grid), dim3(pl.at),
+                               pl.agg_lds_bytes, st,
+                               *q, pl.lay, s.rec, total, chunk,
+                               o->table, o->nslots - 1, (o->nslots * 7) / 8,
+                               o->ctrs, o->err, pl.agg_lds_slots);
+        }
+        if (!piped) tm.record();
+        PCHECK(hipGetLastError());
     }
-    PPCHECK(hipStreamSynchronize(streams[0]));
-    PPCHECK(hipStreamSynchronize(streams[1]));
-    double wall = now_ms() - t0;
-    o->kernel_ms = (float)wall;
-    o->n_kernels = 1;
-    o->t_ms[0] = (float)wall;
-    snprintf(o->k_names[0], 16, "pipeline");
+    /* rows_passed is accumulated by k_part_histo (hot + cold alike) */
+    if (piped) {
+        PCHECK(hipStreamSynchronize(streams[0]));
+        PCHECK(hipStreamSynchronize(streams[1]));
+        double wall = now_ms() - t0;
+        o->kernel_ms = (float)wall;
+        o->n_kernels = 1;
+        o->t_ms[0] = (float)wall;
+        snprintf(o->k_names[0], 16, "pipeline");
+    } else {
+        tm.finish(o, NAMES);    /* waits for the last kernel */
+    }
     cleanup();
-    #undef PPCHECK
+    #undef PCHECK
     return 0;
 }
 
@@ -3507,61 +3507,142 @@ static int run_partitioned_pipe(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
  * and the single fused kernel wins; above it, partition. */
 #define FUSED_MAX_GROUPS 512
 
-/* sort-dedup aggregate (bkdedup.inc, included below): for high-cardinality
+/* Whether bkgpu_filter_agg tries the sort-dedup aggregate (bkdedup.inc) on a
+ * partitioned shape before the dense / hash partition: for high-cardinality
  * GROUP BY and for small/mid row ranges where the partitioned pipeline's
- * fixed passes dominate */
-extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
-                                              int64_t row_begin,
-                                              int64_t row_end);
+ * fixed passes dominate.
+ *
+ * Sort-dedup routing, re-measured at round-2 close: the DENSE pipeline
+ * now beats the sorted path at every plain-GROUP-BY size once a shape
+ * is dense-eligible (c2a shape, same box: 3e7 rows 0.50 vs 1.25 ms,
+ * 1e8 0.68 vs 1.63, 2e8 0.94 vs 2.21; at the 1e9 c2b EQ-selective
+ * shape they tie, 3.018 vs 3.02) — the round-2 staged-load dense work
+ * obsoleted the earlier "sorted ~3x faster at 1e8" measurement this
+ * block was built on. Dense-eligible shapes therefore go dense
+ * outright (BK_DENSE below 1 puts the sorted path first again); the
+ * sorted path remains the route for shapes dense cannot
+ * take (wide key spans, nullable keys) within its range caps, and the
+ * designed path for high-cardinality DISTINCT level 1. An EQUALITY
+ * conjunct still raises the sorted range bound for those shapes (the
+ * reference's index selector uses the same signal,
+ * src/physical_plan/index_selector.cpp), gated on a survivor estimate
+ * from column stats. BK_SORTED_RANGE overrides (0 = off). */
+static bool sorted_first(BkgTable* t, const BkQuerySpec* q, int64_t row_begin,
+                         int64_t row_end, bool use_dense) {
+    int dense_pref = 1;
+    if (const char* e = getenv("BK_DENSE")) dense_pref = atoi(e);
+    if (use_dense && dense_pref >= 1) return false;
+    /* the raised cap applies only when the EQ plausibly SELECTS: a
+     * low-selectivity EQ (2-valued column) over 1e9 rows would
+     * materialize ~5e8 key/rowid records before falling back. Estimate
+     * survivors from column stats (uniform assumption over the encoded
+     * span, EQ conjuncts only — range conjuncts ignored, conservative)
+     * and keep the default cap when the estimate stays huge. */
+    double est = (double)(row_end - row_begin);
+    bool has_eq = false;
+    for (int32_t j = 0; j < q->n_conjuncts; j++)
+        if (q->conjuncts[j].op == BK_OP_EQ) {
+            has_eq = true;
+            int c = q->conjuncts[j].col;
+            if (c >= 0 && c < t->ncols && !q->conjuncts[j].arith &&
+                !q->conjuncts[j].fn && ensure_stats(t, c) == 0 &&
+                t->stat_ok[c]) {
+                uint64_t span = t->stat_max[c] - t->stat_min[c];
+                est /= (double)span + 1.0;
+            }
+        }
+    bool eq_selective = has_eq && est <= 200 * 1000 * 1000.0;
+    int64_t smax = eq_selective ? 1200 * 1000 * 1000ll
+                                : 200 * 1000 * 1000;
+    if (const char* e = getenv("BK_SORTED_RANGE")) smax = atoll(e);
+    return row_end - row_begin <= smax;
+}
 
-
-static int g_debug_timing = -1;
-static bool debug_timing() {
-    if (g_debug_timing < 0) g_debug_timing = getenv("BK_DEBUG") ? 1 : 0;
-    return g_debug_timing == 1;
+/* the single-kernel routes (no GROUP BY, or <= FUSED_MAX_GROUPS expected
+ * groups) for one attempt; returns like run_partitioned */
+static int run_fused(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
+                     int64_t row_begin, int64_t row_end,
+                     int64_t expected_groups) {
+    static const char* NAMES1[] = {"fused_agg"};
+    const int stride = SLOT_HDR + 2 * q->n_aggs;
+    DevCols dc = table_cols(t);
+    EvTimer tm;
+    const int blocks = 2048;
+    if (q->n_group == 0) {
+        /* pre-initialize slot 0 as the single group (state=2, flag 0):
+         * mirrors agg_node.cpp:490-505's always-present row */
+        uint64_t hdr[3] = {2ull /* state=2,flag=0 */, 0, 0};
+        HIP_CHECK(hipMemcpy(o->table, hdr, 24, hipMemcpyHostToDevice));
+        uint64_t one = 1;
+        HIP_CHECK(hipMemcpy(o->ctrs, &one, 8, hipMemcpyHostToDevice));
+        tm.record();
+        auto scal_fn = q->n_aggs <= 4 ? k_filter_agg_scalar<4>
+                                      : k_filter_agg_scalar<8>;
+        hipLaunchKernelGGL(scal_fn, dim3(blocks), dim3(256),
+                           0, 0, dc, *q, row_begin, row_end, o->table,
+                           o->ctrs + 1);
+    } else {
+        /* low-cardinality: 1024-thread blocks (16 waves/CU at the
+         * 135 KB table) took the 300-group 1e9-row shape from 28.7
+         * to 23.3 ms. Per-lane slot REPLICATION is measured DEAD
+         * (R=2 +11%, R=4 +40%: replica probe chains cost more than
+         * the contention they remove); BK_FUSED_REP re-enables it
+         * for experiments. BK_WCOMB_MAX=N opts tiny-cardinality
+         * queries (<= N expected groups) into the WAVE-COMBINE
+         * variant (one masked wave reduction + one leader atomic per
+         * distinct key per 64-row batch) — default OFF: the claim +
+         * shuffle state held across the ballot loop spills 180-240
+         * B/lane scratch and measured 24x SLOWER than the plain
+         * same-address LDS-atomic kernel. */
+        uint32_t rep = 1;
+        if (const char* e = getenv("BK_FUSED_REP")) rep = atoi(e);
+        int64_t wmax = 0;
+        if (const char* e = getenv("BK_WCOMB_MAX")) wmax = atoll(e);
+        tm.record();
+        if (expected_groups <= wmax) {
+            uint32_t wslots = 512;
+            while ((size_t)wslots * stride * 8 > 60 * 1024) wslots >>= 1;
+            size_t wbytes = ((size_t)wslots * stride + 2) * 8;
+            auto wfn = q->n_aggs <= 4 ? k_filter_agg_wcomb<4>
+                                      : k_filter_agg_wcomb<8>;
+            hipLaunchKernelGGL(wfn, dim3(8192), dim3(512), wbytes, 0,
+                               dc, *q, row_begin, row_end, o->table,
+                               o->nslots - 1, (o->nslots * 7) / 8,
+                               o->ctrs, o->ctrs + 1, o->err, wslots);
+        } else {
+            uint32_t lds_slots = 2048;
+            size_t fcap = 135 * 1024;
+            if (const char* e = getenv("BK_FUSED_LDS_KB"))
+                fcap = (size_t)atoi(e) * 1024;
+            while ((size_t)lds_slots * stride * 8 > fcap) lds_slots >>= 1;
+            size_t lds_bytes = ((size_t)lds_slots * stride + 2) * 8;
+            hipLaunchKernelGGL(k_filter_agg_group, dim3(blocks),
+                               dim3(1024), lds_bytes, 0,
+                               dc, *q, row_begin, row_end, o->table,
+                               o->nslots - 1, (o->nslots * 7) / 8,
+                               o->ctrs, o->ctrs + 1, o->err, lds_slots,
+                               rep - 1);
+        }
+    }
+    tm.record();
+    hipError_t lerr = hipGetLastError();
+    if (lerr != hipSuccess) {
+        snprintf(g_err, sizeof g_err, "filter_agg launch: %s",
+                 hipGetErrorString(lerr));
+        return -1;
+    }
+    tm.finish(o, NAMES1);
+    return 0;
 }
 
 extern "C" BkgAggOut* bkgpu_filter_agg(BkgTable* t, const BkQuerySpec* q,
                                        int64_t row_begin, int64_t row_end,
                                        int64_t expected_groups) {
-    if (q && pack_key_words(q) > 2) {
-        set_err("group keys exceed two packed 64-bit words "
-                "(set group_bits per key, bk_common.h)");
-        return nullptr;
-    }
-    if (q)
-        for (int32_t k = 0; k < q->n_group; k++)
-            if (q->group_bits[k] &&
-                (q->group_bits[k] < 0 || q->group_bits[k] > 63 ||
-                 q->group_types[k] == BK_DOUBLE)) {
-                set_err("bad group_bits (1..63; DOUBLE keys need bits==0)");
-                return nullptr;
-            }
-    if (q)
-        for (int32_t k = 0; k < q->n_group; k++)
-            if (q->group_fns[k] && q->group_types[k] != BK_INT64 &&
-                q->group_types[k] != BK_DATETIME) {
-                set_err("group_fns need an int64/DATETIME key column");
-                return nullptr;
-            }
-    if (q)
-        for (int32_t j = 0; j < q->n_conjuncts; j++)
-            if (q->conjuncts[j].or_group < 0 || q->conjuncts[j].or_group > 31) {
-                /* kernels and oracle fold clause ids with & 31 — ids
-                 * congruent mod 32 would silently merge into one clause */
-                set_err("or_group out of range (0..31)");
-                return nullptr;
-            }
-    /* postfix programs + legacy arith slots (query_exprs_check) */
-    if (q && t && query_exprs_check(t, q) != 0) return nullptr;
+    if (query_shape_check(t, q) != 0) return nullptr;
     if (ensure_device() != 0) return nullptr;
     double t_start = debug_timing() ? now_ms() : 0;
     double t_alloc = 0, t_pipe = 0;
-    BkgAggOut* o = new BkgAggOut();
-    o->q = *q;
-    const int stride = SLOT_HDR + 2 * q->n_aggs;
     int64_t nslots = next_pow2(std::max<int64_t>(1024, expected_groups * 2));
-    DevCols dc = table_cols(t);
     bool partitioned = q->n_group > 0 && expected_groups > FUSED_MAX_GROUPS &&
                        row_end > row_begin;
 
@@ -3569,148 +3650,35 @@ extern "C" BkgAggOut* bkgpu_filter_agg(BkgTable* t, const BkQuerySpec* q,
      * aggregate into a range partition + direct-indexed LDS accumulate (no
      * hash probes / claim chains). Preferred at large ranges; BK_DENSE=0
      * disables, BK_DENSE=2 prefers it at every range. */
-    bool use_dense = false;
     DenseSpec dsp;
     DRecLayout dlay;
-    if (partitioned && dense_eligible(t, q, &dsp, &dlay)) use_dense = true;
-    int dense_pref = 1;
-    if (const char* e = getenv("BK_DENSE")) dense_pref = atoi(e);
+    bool use_dense = partitioned && dense_eligible(t, q, &dsp, &dlay);
 
-    /* Sort-dedup routing, re-measured at round-2 close: the DENSE pipeline
-     * now beats the sorted path at every plain-GROUP-BY size once a shape
-     * is dense-eligible (c2a shape, same box: 3e7 rows 0.50 vs 1.25 ms,
-     * 1e8 0.68 vs 1.63, 2e8 0.94 vs 2.21; at the 1e9 c2b EQ-selective
-     * shape they tie, 3.018 vs 3.02) — the round-2 staged-load dense work
-     * obsoleted the earlier "sorted ~3x faster at 1e8" measurement this
-     * block was built on. Dense-eligible shapes therefore go dense
-     * outright; the sorted path remains the route for shapes dense cannot
-     * take (wide key spans, nullable keys) within its range caps, and the
-     * designed path for high-cardinality DISTINCT level 1. An EQUALITY
-     * conjunct still raises the sorted range bound for those shapes (the
-     * reference's index selector uses the same signal,
-     * src/physical_plan/index_selector.cpp), gated on a survivor estimate
-     * from column stats. BK_SORTED_RANGE overrides (0 = off). */
-    if (partitioned) {
-        /* the raised cap applies only when the EQ plausibly SELECTS: a
-         * low-selectivity EQ (2-valued column) over 1e9 rows would
-         * materialize ~5e8 key/rowid records before falling back. Estimate
-         * survivors from column stats (uniform assumption over the encoded
-         * span, EQ conjuncts only — range conjuncts ignored, conservative)
-         * and keep the default cap when the estimate stays huge. */
-        double est = (double)(row_end - row_begin);
-        bool has_eq = false;
-        for (int32_t j = 0; j < q->n_conjuncts; j++)
-            if (q->conjuncts[j].op == BK_OP_EQ) {
-                has_eq = true;
-                int c = q->conjuncts[j].col;
-                if (c >= 0 && c < t->ncols && !q->conjuncts[j].arith &&
-                    !q->conjuncts[j].fn && ensure_stats(t, c) == 0 &&
-                    t->stat_ok[c]) {
-                    uint64_t span = t->stat_max[c] - t->stat_min[c];
-                    est /= (double)span + 1.0;
-                }
-            }
-        bool eq_selective = has_eq && est <= 200 * 1000 * 1000.0;
-        int64_t smax = eq_selective ? 1200 * 1000 * 1000ll
-                                    : 200 * 1000 * 1000;
-        if (const char* e = getenv("BK_SORTED_RANGE")) smax = atoll(e);
-        bool dense_first = use_dense && dense_pref >= 1;
-        if (!dense_first && row_end - row_begin <= smax) {
-            BkgAggOut* so = bkgpu_filter_agg_sorted(t, q, row_begin, row_end);
-            if (so) { delete o; return so; }
-            g_err[0] = 0;   /* shape did not qualify — partitioned path */
-        }
+    if (partitioned && sorted_first(t, q, row_begin, row_end, use_dense)) {
+        BkgAggOut* so = bkgpu_filter_agg_sorted(t, q, row_begin, row_end);
+        if (so) return so;
+        g_err[0] = 0;   /* shape did not qualify — partitioned path */
     }
 
+    BkgAggOut* o = new BkgAggOut();
+    o->q = *q;
     for (int attempt = 0; attempt < 8; attempt++) {
         /* dense mode never touches the hash table during aggregation (a
          * 16-slot stub keeps downstream code paths non-null; dense_to_hash
          * re-allocates at the real size if merge/rollup need it) */
-        if (agg_alloc(o, partitioned && use_dense ? 16 : nslots) != 0) {
+        if (agg_alloc(o, use_dense ? 16 : nslots) != 0) {
             bkgpu_agg_free(o);
             return nullptr;
         }
         if (debug_timing()) { (void)hipDeviceSynchronize(); t_alloc = now_ms(); }
-        int blocks = 2048, threads = 256;
-        if (partitioned && use_dense) {
-            if (run_dense(o, t, q, dsp, dlay, row_begin, row_end) != 0) {
-                bkgpu_agg_free(o);
-                return nullptr;
-            }
-        } else if (partitioned) {
-            if (run_partitioned(o, t, q, row_begin, row_end, expected_groups) != 0) {
-                bkgpu_agg_free(o);
-                return nullptr;
-            }
-        } else {
-            static const char* NAMES1[] = {"fused_agg"};
-            EvTimer tm;
-            uint32_t lds_slots = 2048;
-            size_t fcap = 135 * 1024;
-            if (const char* e = getenv("BK_FUSED_LDS_KB"))
-                fcap = (size_t)atoi(e) * 1024;
-            while ((size_t)lds_slots * stride * 8 > fcap) lds_slots >>= 1;
-            size_t lds_bytes = ((size_t)lds_slots * stride + 2) * 8;
-            if (q->n_group > 0) threads = 1024;   /* 16 waves at 1 block/CU */
-            if (q->n_group == 0) {
-                /* pre-initialize slot 0 as the single group (state=2, flag 0):
-                 * mirrors agg_node.cpp:490-505's always-present row */
-                uint64_t hdr[3] = {2ull /* state=2,flag=0 */, 0, 0};
-                HIP_CHECK_NULL(hipMemcpy(o->table, hdr, 24, hipMemcpyHostToDevice));
-                uint64_t one = 1;
-                HIP_CHECK_NULL(hipMemcpy(o->ctrs, &one, 8, hipMemcpyHostToDevice));
-                tm.record();
-                auto scal_fn = q->n_aggs <= 4 ? k_filter_agg_scalar<4>
-                                              : k_filter_agg_scalar<8>;
-                hipLaunchKernelGGL(scal_fn, dim3(blocks), dim3(threads),
-                                   0, 0, dc, *q, row_begin, row_end, o->table,
-                                   o->ctrs + 1);
-            } else {
-                /* low-cardinality: 1024-thread blocks (16 waves/CU at the
-                 * 135 KB table) took the 300-group 1e9-row shape from 28.7
-                 * to 23.3 ms. Per-lane slot REPLICATION is measured DEAD
-                 * (R=2 +11%, R=4 +40%: replica probe chains cost more than
-                 * the contention they remove); BK_FUSED_REP re-enables it
-                 * for experiments. BK_WCOMB_MAX=N opts tiny-cardinality
-                 * queries (<= N expected groups) into the WAVE-COMBINE
-                 * variant (one masked wave reduction + one leader atomic per
-                 * distinct key per 64-row batch) — default OFF: the claim +
-                 * shuffle state held across the ballot loop spills 180-240
-                 * B/lane scratch and measured 24x SLOWER than the plain
-                 * same-address LDS-atomic kernel. */
-                uint32_t rep = 1;
-                if (const char* e = getenv("BK_FUSED_REP")) rep = atoi(e);
-                int64_t wmax = 0;
-                if (const char* e = getenv("BK_WCOMB_MAX")) wmax = atoll(e);
-                tm.record();
-                if (expected_groups <= wmax) {
-                    uint32_t wslots = 512;
-                    while ((size_t)wslots * stride * 8 > 60 * 1024) wslots >>= 1;
-                    size_t wbytes = ((size_t)wslots * stride + 2) * 8;
-                    auto wfn = q->n_aggs <= 4 ? k_filter_agg_wcomb<4>
-                                              : k_filter_agg_wcomb<8>;
-                    hipLaunchKernelGGL(wfn, dim3(8192), dim3(512), wbytes, 0,
-                                       dc, *q, row_begin, row_end, o->table,
-                                       o->nslots - 1, (o->nslots * 7) / 8,
-                                       o->ctrs, o->ctrs + 1, o->err, wslots);
-                } else {
-                    hipLaunchKernelGGL(k_filter_agg_group, dim3(blocks),
-                                       dim3(threads), lds_bytes, 0,
-                                       dc, *q, row_begin, row_end, o->table,
-                                       o->nslots - 1, (o->nslots * 7) / 8,
-                                       o->ctrs, o->ctrs + 1, o->err, lds_slots,
-                                       rep - 1);
-                }
-            }
-            tm.record();
-            hipError_t lerr = hipGetLastError();
-            if (lerr != hipSuccess) {
-                snprintf(g_err, sizeof g_err, "filter_agg launch: %s",
-                         hipGetErrorString(lerr));
-                bkgpu_agg_free(o);
-                return nullptr;
-            }
-            tm.finish(o, NAMES1);
+        int rc = use_dense
+            ? run_dense(o, t, q, dsp, dlay, row_begin, row_end)
+            : partitioned
+                ? run_partitioned(o, t, q, row_begin, row_end, expected_groups)
+                : run_fused(o, t, q, row_begin, row_end, expected_groups);
+        if (rc != 0) {
+            bkgpu_agg_free(o);
+            return nullptr;
         }
         uint32_t err_host = 0;
         HIP_CHECK_NULL(hipMemcpy(&err_host, o->err, 4, hipMemcpyDeviceToHost));

@@ -17,6 +17,7 @@
 #   - BK_MAT_SPLIT: gated at >= 3e7 rows, unreachable at test size.
 #   - BK_FUSED_REP / BK_WCOMB_MAX: covered in test_gpu_agg.py.
 #   - multi-GPU exchange, window functions.
+import ctypes as C
 import os
 import re
 
@@ -494,6 +495,14 @@ def test_paired_scatter(world, monkeypatch, sh, g):
     run_route(world, monkeypatch, sh, kn(HASH, BK_PAIR=1, **g), PART)
 
 
+@gpu
+@pytest.mark.parametrize("sh", [S1, S4], ids=repr)
+def test_pairing_ignored_when_pipelined(world, monkeypatch, sh):
+    """Pair staging belongs to the single-pass form: with BK_PIPE the
+    two-stream form runs, unpaired, and gives the same result."""
+    run_route(world, monkeypatch, sh, kn(HASH, BK_PAIR=1, BK_PIPE=2), PIPE)
+
+
 # ---- generic twins of the SIMPLE specialisations ----------------------------
 @gpu
 @pytest.mark.parametrize("sh", [S1, S3_M1, S3_K1, S3_F2], ids=repr)
@@ -675,6 +684,38 @@ def test_sorted_declared_bits_key32(world, monkeypatch, key, g):
     run_route(world, monkeypatch, SB[key], g, SORTED, sorted_path=True)
     run_route(world, monkeypatch, SB[key], g, SORTED, rng=(7, SB[key].n - 3),
               sorted_path=True)
+
+
+@gpu
+def test_sorted_entry_refuses_like_filter_agg(world):
+    """bkgpu_filter_agg_sorted called directly checks the query shape like
+    bkgpu_filter_agg: a clause id of 32 (the kernels fold ids with & 31, so it
+    would merge into clause 0) and a group function (YEAR) on a dict key are
+    refused by both, with the same message."""
+    from baikaldb_amd import QueryPlan
+    sh = S4_20
+    t = world.table(sh)
+    lib = world.eng.lib
+
+    def or_group_32(q):
+        q.conjuncts[1].or_group = 32
+
+    def group_fn_on_dict_key(q):
+        q.group_fns[0], q.group_types[0] = 1, STR
+
+    for spoil in (or_group_32, group_fn_on_dict_key):
+        q = QueryPlan(t.col_types, conjuncts=sh.conj, group=sh.group,
+                      aggs=sh.aggs).to_spec()
+        spoil(q)
+        errs = []
+        for entry, args in ((lib.bkgpu_filter_agg_sorted, (0, sh.n)),
+                            (lib.bkgpu_filter_agg, (0, sh.n, sh.eg))):
+            h = entry(t.handle, C.byref(q), *args)
+            if h:
+                lib.bkgpu_agg_free(h)
+            assert not h, f"{spoil.__name__}: a bad query spec was accepted"
+            errs.append(lib.bkgpu_last_error().decode())
+        assert errs[0] and errs[0] == errs[1], (spoil.__name__, errs)
 
 
 # ---- top-N routes -----------------------------------------------------------
