@@ -364,10 +364,14 @@ __global__ void k_dedup_heads(const KeyT* keys, uint64_t n, uint32_t* f) {
         f[i] = (i == 0) || (keys[i] != keys[i - 1]);
 }
 
-/* flush one locally-accumulated run into its slot (same atomic op set as
- * agg_update_slot, with merged addends — one atomic per agg word per RUN
- * instead of per row: sorted input makes same-slot runs adjacent, and
- * per-row atomics serialize ~26-deep on config2-shaped group sizes). */
+/* flush one locally-accumulated run into its slot: one atomic per agg word
+ * per RUN instead of per row (sorted input makes same-slot runs adjacent,
+ * and per-row atomics serialize ~26-deep on config2-shaped group sizes).
+ * This is agg_part_fold<false> (bkgpu.hip) spelled out over the three
+ * accumulator arrays, and the arms of k_dedup_emit below are
+ * agg_part_of_row (and its twin over a record) spelled out: through helpers
+ * k_dedup_emit<8, uint32, true> gains 20 B/lane of scratch, or the whole
+ * kernel is re-allocated and measured slower. Keep them in step. */
 template <int NA>
 __device__ __forceinline__ void dedup_flush_run(
         uint64_t* slot, const BkQuerySpec& q, const uint64_t* accv,
@@ -591,9 +595,9 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
     if (!t || !q || q->n_group < 1) { set_err("sorted: need GROUP BY"); return nullptr; }
     if (query_shape_check(t, q) != 0) return nullptr;
     SortPack sp{};
+    const BkKeyLayout kl = bk_key_layout(q);
     int bits_total = 0;
-    for (int32_t k = 0; k < q->n_group; k++)
-        bits_total += q->group_bits[k] ? q->group_bits[k] : 64;
+    for (int32_t k = 0; k < kl.n; k++) bits_total += kl.bits[k];
     if (bits_total > 56) {
         /* no usable declared widths: AUTO-pack from column stats (per-key
          * encoding span; works for INT64/DATETIME/DOUBLE/dict encodings

@@ -32,6 +32,7 @@
 #include "../../include/bk_common.h"
 #include "../../include/bk_like.h"
 #include "../../include/bk_keyenc.h"
+#include "../../include/bk_keylayout.h"
 #include "../../include/bk_datagen.h"
 #include "../../include/bkgpu.h"
 #include "../../include/bk_exec.h"
@@ -357,18 +358,6 @@ struct FetchedGroups {
     std::vector<uint8_t> out_has;
 };
 
-/* output tag of an aggregate (finalize types, agg_fn_call.cpp:927-975) */
-static int32_t agg_out_type(int agg_type, int32_t in_type) {
-    switch (agg_type) {
-        case BK_AGG_COUNT_STAR:
-        case BK_AGG_COUNT:
-        case BK_AGG_COUNT_DISTINCT: return BK_INT64;  /* agg_fn_call.cpp:96-99 */
-        case BK_AGG_AVG:
-        case BK_AGG_AVG_DISTINCT: return BK_DOUBLE;
-        default:           return in_type;  /* SUM/MIN/MAX keep input type */
-    }
-}
-
 /* ---- AggNode (agg_node.cpp:405-587). open() drains the child pipeline —
  * here: compiles {scan, filter, group, aggs} into one bkgpu_filter_agg call
  * (the Acero-slot pattern, region.cpp:2793) — and get_next() emits finalized
@@ -409,7 +398,7 @@ private:
             const bool key = c < _q.n_group;
             const int a = c - _q.n_group;
             const int32_t ty = key ? _q.group_types[c]
-                : agg_out_type(_q.aggs[a].agg_type, _q.agg_in_types[a]);
+                : bk_agg_out_type(_q.aggs[a].agg_type, _q.agg_in_types[a]);
             specs[c].col_type = ty;
             int32_t* d32 = (int32_t*)data[c].data();
             for (int64_t g = 0; g < n; g++) {
@@ -680,7 +669,7 @@ public:
             }
             for (int a = 0; a < _q.n_aggs; a++, s++) {
                 ExprValue v;
-                v.type = agg_out_type(_q.aggs[a].agg_type, _q.agg_in_types[a]);
+                v.type = bk_agg_out_type(_q.aggs[a].agg_type, _q.agg_in_types[a]);
                 size_t idx = (size_t)a * _g.n + _iter;
                 if (!_g.out_has[idx]) {
                     v.is_null_ = true;

@@ -46,6 +46,7 @@
 #include "../../include/bk_common.h"
 #include "../../include/bk_datagen.h"
 #include "../../include/bk_keyenc.h"
+#include "../../include/bk_keylayout.h"
 #include "../../include/bkgpu.h"
 
 /* ------------------------------------------------------------------ */
@@ -660,7 +661,11 @@ __device__ __forceinline__ uint64_t agg_enc(const DevCols& cols,
  * 64-bit word. With <= 2 keys and all-zero bits this degenerates to the
  * plain [k0][k1] layout (shift stays 0, each key takes its own word).
  * Widths come from the QUERY, never from data statistics, so the packed
- * keys are identical on every rank and partial blobs merge across GPUs. */
+ * keys are identical on every rank and partial blobs merge across GPUs.
+ * This is the row path's in-register copy of the walk in bk_key_layout
+ * (bk_keylayout.h), which every reader of the packed words uses: the two
+ * must stay in step (tests/test_gpu_keylayout.py compares them through the
+ * oracle). */
 struct KeyPack { uint64_t k0, k1; uint32_t flag; };
 
 template <bool SIMPLE = false>
@@ -704,42 +709,130 @@ __device__ __forceinline__ void atomic_add_f64_lds(uint64_t* addr, double v) {
     unsafeAtomicAdd((double*)addr, v);   /* ds_add_f64 */
 }
 
-__device__ __forceinline__ void dedup_flush_run_arrays(
-        uint64_t* slot, const BkQuerySpec& q, const uint64_t* accv,
-        const uint64_t* accc, const double* accd, int na) {
-    for (int32_t a = 0; a < na; a++) {
-        if (a >= q.n_aggs) break;
-        uint64_t* val = slot + SLOT_HDR + 2 * a;
-        uint64_t* cnt = val + 1;
-        int at = q.aggs[a].agg_type;
-        switch (at) {
-            case BK_AGG_COUNT_STAR:
-            case BK_AGG_COUNT:
-                if (accv[a])
-                    atomicAdd((unsigned long long*)val,
-                              (unsigned long long)accv[a]);
-                break;
-            case BK_AGG_MIN:
-            case BK_AGG_MAX:
-                if (accc[a]) {
-                    atomicMax((unsigned long long*)val,
-                              (unsigned long long)accv[a]);
-                    atomicAdd((unsigned long long*)cnt,
-                              (unsigned long long)accc[a]);
-                }
-                break;
-            default:  /* SUM / AVG */
-                if (accc[a]) {
-                    if (q.agg_in_types[a] == BK_DOUBLE || at == BK_AGG_AVG)
-                        atomic_add_f64_global(val, accd[a]);
-                    else
-                        atomicAdd((unsigned long long*)val,
-                                  (unsigned long long)accv[a]);
-                    atomicAdd((unsigned long long*)cnt,
-                              (unsigned long long)accc[a]);
-                }
-                break;
+/* ---- partial aggregate: what one row, one record, a wave's worth of either,
+ * or a stored state contributes to ONE aggregate of a slot. v = count
+ * (COUNT kinds), complemented/plain encoding (MIN/MAX) or wrapping int sum;
+ * c = non-NULL inputs; d = f64 sum. Fields a kind does not use stay 0. ---- */
+struct AggPart { uint64_t v, c; double d; };
+
+/* SUM/AVG kinds whose value word holds an f64 */
+__device__ __forceinline__ bool agg_sums_f64(const BkQuerySpec& q, int a) {
+    const int at = q.aggs[a].agg_type;
+    return q.agg_in_types[a] == BK_DOUBLE || at == BK_AGG_AVG ||
+           at == BK_AGG_AVG_DISTINCT;
+}
+
+/* row r's contribution to aggregate a */
+__device__ __forceinline__ AggPart agg_part_of_row(const DevCols& cols,
+                                                   const BkQuerySpec& q,
+                                                   int a, int64_t r) {
+    AggPart p{0, 0, 0.0};
+    const BkAggSpec& as = q.aggs[a];
+    const int32_t vt = q.agg_in_types[a];
+    switch (as.agg_type) {
+        case BK_AGG_COUNT_STAR: p.v = 1; break;
+        case BK_AGG_COUNT:
+            p.v = agg_input(cols, q, as, vt, r).valid ? 1 : 0;
+            break;
+        case BK_AGG_SUM: {
+            AggIn v = agg_input(cols, q, as, vt, r);
+            if (!v.valid) break;
+            if (vt == BK_DOUBLE) p.d = v.d;
+            else p.v = (uint64_t)v.i;
+            p.c = 1;
+            break;
         }
+        case BK_AGG_AVG: {
+            AggIn v = agg_input(cols, q, as, vt, r);
+            if (!v.valid) break;
+            p.d = v.d;
+            p.c = 1;
+            break;
+        }
+        case BK_AGG_MIN: {
+            AggIn v = agg_input(cols, q, as, vt, r);
+            if (!v.valid) break;
+            p.v = ~agg_enc(cols, as, vt, v, r);
+            p.c = 1;
+            break;
+        }
+        case BK_AGG_MAX: {
+            AggIn v = agg_input(cols, q, as, vt, r);
+            if (!v.valid) break;
+            p.v = agg_enc(cols, as, vt, v, r);
+            p.c = 1;
+            break;
+        }
+        default: break;
+    }
+    return p;
+}
+
+/* a stored state {val, cnt} is a partial too (MERGE_AGG, agg_node.cpp:539) */
+__device__ __forceinline__ AggPart agg_part_of_state(uint64_t sv, uint64_t sc) {
+    AggPart p{sv, sc, 0.0};
+    memcpy(&p.d, &sv, 8);
+    return p;
+}
+
+/* x then y */
+__device__ __forceinline__ AggPart agg_part_join(int at, AggPart x,
+                                                 const AggPart& y) {
+    if (at == BK_AGG_MIN || at == BK_AGG_MAX) x.v = x.v > y.v ? x.v : y.v;
+    else x.v += y.v;
+    x.c += y.c;
+    x.d += y.d;
+    return x;
+}
+
+/* another lane's partial, for the wave reductions */
+enum { SHFL_DOWN, SHFL_XOR };
+template <int MODE>
+__device__ __forceinline__ AggPart agg_part_shfl(const AggPart& p, int off) {
+    if (MODE == SHFL_DOWN)
+        return AggPart{__shfl_down(p.v, off, 64), __shfl_down(p.c, off, 64),
+                       __shfl_down(p.d, off, 64)};
+    return AggPart{__shfl_xor(p.v, off, 64), __shfl_xor(p.c, off, 64),
+                   __shfl_xor(p.d, off, 64)};
+}
+
+/* fold a partial into aggregate a of a slot: the one atomic op set. Empty
+ * partials (zero count) touch nothing. */
+template <bool LDS>
+__device__ __forceinline__ void agg_part_fold(uint64_t* slot,
+                                              const BkQuerySpec& q, int a,
+                                              const AggPart& p) {
+    uint64_t* val = slot + SLOT_HDR + 2 * a;
+    uint64_t* cnt = val + 1;
+    switch (q.aggs[a].agg_type) {
+        case BK_AGG_COUNT_STAR:
+        case BK_AGG_COUNT:
+        case BK_AGG_COUNT_DISTINCT:  /* additive; ranks exchange at L1 */
+            if (p.v) atomicAdd((unsigned long long*)val, (unsigned long long)p.v);
+            break;
+        case BK_AGG_MIN:
+        case BK_AGG_MAX:
+            if (p.c) {
+                atomicMax((unsigned long long*)val, (unsigned long long)p.v);
+                atomicAdd((unsigned long long*)cnt, (unsigned long long)p.c);
+            }
+            break;
+        case BK_AGG_SUM:
+        case BK_AGG_AVG:
+        case BK_AGG_SUM_DISTINCT:
+        case BK_AGG_AVG_DISTINCT:
+            if (p.c) {
+                if (agg_sums_f64(q, a)) {
+                    if (LDS) atomic_add_f64_lds(val, p.d);
+                    else     atomic_add_f64_global(val, p.d);
+                } else {
+                    atomicAdd((unsigned long long*)val,
+                              (unsigned long long)p.v);   /* int64 wrap */
+                }
+                atomicAdd((unsigned long long*)cnt, (unsigned long long)p.c);
+            }
+            break;
+        default: break;
     }
 }
 
@@ -813,42 +906,8 @@ __device__ __forceinline__ void agg_merge_slot(uint64_t* dst, const uint64_t* sr
     #pragma unroll
     for (int32_t a = 0; a < BK_MAX_AGGS; a++) {
         if (a >= q.n_aggs) break;
-        uint64_t* val = dst + SLOT_HDR + 2 * a;
-        uint64_t* cnt = val + 1;
-        uint64_t sv = src[2 * a];
-        uint64_t sc = src[2 * a + 1];
-        switch (q.aggs[a].agg_type) {
-            case BK_AGG_COUNT_STAR:
-            case BK_AGG_COUNT:
-            case BK_AGG_COUNT_DISTINCT:  /* additive; ranks exchange at L1 */
-                if (sv) atomicAdd((unsigned long long*)val, (unsigned long long)sv);
-                break;
-            case BK_AGG_SUM:
-            case BK_AGG_AVG:
-            case BK_AGG_SUM_DISTINCT:
-            case BK_AGG_AVG_DISTINCT:
-                if (sc) {
-                    if (q.agg_in_types[a] == BK_DOUBLE ||
-                        q.aggs[a].agg_type == BK_AGG_AVG ||
-                        q.aggs[a].agg_type == BK_AGG_AVG_DISTINCT) {
-                        double d; memcpy(&d, &sv, 8);
-                        if (LDS) atomic_add_f64_lds(val, d);
-                        else     atomic_add_f64_global(val, d);
-                    } else {
-                        atomicAdd((unsigned long long*)val, (unsigned long long)sv);
-                    }
-                    atomicAdd((unsigned long long*)cnt, (unsigned long long)sc);
-                }
-                break;
-            case BK_AGG_MIN:
-            case BK_AGG_MAX:
-                if (sc) {
-                    atomicMax((unsigned long long*)val, (unsigned long long)sv);
-                    atomicAdd((unsigned long long*)cnt, (unsigned long long)sc);
-                }
-                break;
-            default: break;
-        }
+        agg_part_fold<LDS>(dst, q, a,
+                           agg_part_of_state(src[2 * a], src[2 * a + 1]));
     }
 }
 
@@ -1044,56 +1103,57 @@ __global__ void __launch_bounds__(256)
 k_filter_agg_scalar(DevCols cols, BkQuerySpec q, int64_t row_begin, int64_t row_end,
                     uint64_t* gtable, uint64_t* rows_passed) {
     int64_t my_passed = 0;
-    uint64_t acc_v[NA];   /* wrapping-int or cnt accum; doubles separate */
-    uint64_t acc_c[NA];
-    double   acc_d[NA];
+    AggPart acc[NA];
     #pragma unroll
-    for (int a = 0; a < NA; a++) { acc_v[a] = 0; acc_c[a] = 0; acc_d[a] = 0.0; }
+    for (int a = 0; a < NA; a++) acc[a] = AggPart{0, 0, 0.0};
 
     int64_t gstride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t r = row_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
          r < row_end; r += gstride) {
         if (!row_passes(cols, q, r)) continue;
         my_passed++;
+        /* join(acc, agg_part_of_row) spelled out per kind: NA = 8 sits at
+         * 247 VGPRs, and the generic form takes it past 256 (occupancy
+         * 2 -> 1) */
         #pragma unroll
         for (int32_t a = 0; a < NA; a++) {
             if (a >= q.n_aggs) break;
             const BkAggSpec& as = q.aggs[a];
             switch (as.agg_type) {
-                case BK_AGG_COUNT_STAR: acc_v[a]++; break;
+                case BK_AGG_COUNT_STAR: acc[a].v++; break;
                 case BK_AGG_COUNT:
                     if (agg_input(cols, q, as, q.agg_in_types[a], r).valid)
-                        acc_v[a]++;
+                        acc[a].v++;
                     break;
                 case BK_AGG_SUM: {
                     AggIn v = agg_input(cols, q, as, q.agg_in_types[a], r);
                     if (!v.valid) break;
-                    if (q.agg_in_types[a] == BK_DOUBLE) acc_d[a] += v.d;
-                    else acc_v[a] += (uint64_t)v.i;
-                    acc_c[a]++;
+                    if (q.agg_in_types[a] == BK_DOUBLE) acc[a].d += v.d;
+                    else acc[a].v += (uint64_t)v.i;
+                    acc[a].c++;
                     break;
                 }
                 case BK_AGG_AVG: {
                     AggIn v = agg_input(cols, q, as, q.agg_in_types[a], r);
                     if (!v.valid) break;
-                    acc_d[a] += v.d;
-                    acc_c[a]++;
+                    acc[a].d += v.d;
+                    acc[a].c++;
                     break;
                 }
                 case BK_AGG_MIN: {
                     AggIn v = agg_input(cols, q, as, q.agg_in_types[a], r);
                     if (!v.valid) break;
                     uint64_t e = ~agg_enc(cols, as, q.agg_in_types[a], v, r);
-                    if (e > acc_v[a]) acc_v[a] = e;
-                    acc_c[a]++;
+                    if (e > acc[a].v) acc[a].v = e;
+                    acc[a].c++;
                     break;
                 }
                 case BK_AGG_MAX: {
                     AggIn v = agg_input(cols, q, as, q.agg_in_types[a], r);
                     if (!v.valid) break;
                     uint64_t e = agg_enc(cols, as, q.agg_in_types[a], v, r);
-                    if (e > acc_v[a]) acc_v[a] = e;
-                    acc_c[a]++;
+                    if (e > acc[a].v) acc[a].v = e;
+                    acc[a].c++;
                     break;
                 }
                 default: break;
@@ -1105,40 +1165,17 @@ k_filter_agg_scalar(DevCols cols, BkQuerySpec q, int64_t row_begin, int64_t row_
     #pragma unroll
     for (int32_t a = 0; a < NA; a++) {
         if (a >= q.n_aggs) break;
-        int at = q.aggs[a].agg_type;
-        for (int off = 32; off > 0; off >>= 1) {
-            uint64_t ov = __shfl_down(acc_v[a], off, 64);
-            acc_c[a] += __shfl_down(acc_c[a], off, 64);
-            acc_d[a] += __shfl_down(acc_d[a], off, 64);
-            if (at == BK_AGG_MIN || at == BK_AGG_MAX) acc_v[a] = acc_v[a] > ov ? acc_v[a] : ov;
-            else acc_v[a] += ov;
-        }
+        for (int off = 32; off > 0; off >>= 1)
+            acc[a] = agg_part_join(q.aggs[a].agg_type, acc[a],
+                                   agg_part_shfl<SHFL_DOWN>(acc[a], off));
     }
     if ((threadIdx.x & 63) == 0) {
         atomicAdd((unsigned long long*)rows_passed, (unsigned long long)my_passed);
-        uint64_t* s = gtable;  /* slot 0, pre-initialized state=2 flag=0 */
+        /* slot 0, pre-initialized state=2 flag=0 */
         #pragma unroll
         for (int32_t a = 0; a < NA; a++) {
             if (a >= q.n_aggs) break;
-            uint64_t* val = s + SLOT_HDR + 2 * a;
-            uint64_t* cnt = val + 1;
-            int at = q.aggs[a].agg_type;
-            if (at == BK_AGG_COUNT_STAR || at == BK_AGG_COUNT) {
-                if (acc_v[a]) atomicAdd((unsigned long long*)val, (unsigned long long)acc_v[a]);
-            } else if (at == BK_AGG_MIN || at == BK_AGG_MAX) {
-                if (acc_c[a]) {
-                    atomicMax((unsigned long long*)val, (unsigned long long)acc_v[a]);
-                    atomicAdd((unsigned long long*)cnt, (unsigned long long)acc_c[a]);
-                }
-            } else {  /* SUM / AVG */
-                if (acc_c[a]) {
-                    if (q.agg_in_types[a] == BK_DOUBLE || at == BK_AGG_AVG)
-                        atomic_add_f64_global(val, acc_d[a]);
-                    else
-                        atomicAdd((unsigned long long*)val, (unsigned long long)acc_v[a]);
-                    atomicAdd((unsigned long long*)cnt, (unsigned long long)acc_c[a]);
-                }
-            }
+            agg_part_fold<false>(gtable, q, a, acc[a]);
         }
     }
 }
@@ -1199,81 +1236,14 @@ k_filter_agg_wcomb(DevCols cols, BkQuerySpec q, int64_t row_begin,
             #pragma unroll
             for (int32_t a = 0; a < NA; a++) {
                 if (a >= q.n_aggs) break;
-                const BkAggSpec& as = q.aggs[a];
-                int at = as.agg_type;
-                bool im = (at == BK_AGG_MIN || at == BK_AGG_MAX);
-                uint64_t tv = 0;
-                uint64_t tc = 0;
-                double td = 0.0;
-                if (mine) {
-                    switch (at) {
-                        case BK_AGG_COUNT_STAR: tv = 1; break;
-                        case BK_AGG_COUNT:
-                            tv = agg_input(cols, q, as, q.agg_in_types[a], r)
-                                     .valid ? 1 : 0;
-                            break;
-                        case BK_AGG_SUM: {
-                            AggIn v = agg_input(cols, q, as, q.agg_in_types[a], r);
-                            if (!v.valid) break;
-                            if (q.agg_in_types[a] == BK_DOUBLE) td = v.d;
-                            else tv = (uint64_t)v.i;
-                            tc = 1;
-                            break;
-                        }
-                        case BK_AGG_AVG: {
-                            AggIn v = agg_input(cols, q, as, q.agg_in_types[a], r);
-                            if (!v.valid) break;
-                            td = v.d;
-                            tc = 1;
-                            break;
-                        }
-                        case BK_AGG_MIN: {
-                            AggIn v = agg_input(cols, q, as, q.agg_in_types[a], r);
-                            if (!v.valid) break;
-                            tv = ~agg_enc(cols, as, q.agg_in_types[a], v, r);
-                            tc = 1;
-                            break;
-                        }
-                        case BK_AGG_MAX: {
-                            AggIn v = agg_input(cols, q, as, q.agg_in_types[a], r);
-                            if (!v.valid) break;
-                            tv = agg_enc(cols, as, q.agg_in_types[a], v, r);
-                            tc = 1;
-                            break;
-                        }
-                        default: break;
-                    }
-                }
+                AggPart t{0, 0, 0.0};
+                if (mine) t = agg_part_of_row(cols, q, a, r);
                 #pragma unroll
-                for (int off = 32; off > 0; off >>= 1) {
-                    uint64_t ov = __shfl_xor((unsigned long long)tv, off, 64);
-                    tc += __shfl_xor((unsigned long long)tc, off, 64);
-                    td += __shfl_xor(td, off, 64);
-                    tv = im ? (tv > ov ? tv : ov) : tv + ov;
-                }
-                if (lane == leader && slot) {
-                    uint64_t* val = slot + SLOT_HDR + 2 * a;
-                    uint64_t* cnt = val + 1;
-                    if (at == BK_AGG_COUNT_STAR || at == BK_AGG_COUNT) {
-                        if (tv) atomicAdd((unsigned long long*)val,
-                                          (unsigned long long)tv);
-                    } else if (im) {
-                        if (tc) {
-                            atomicMax((unsigned long long*)val,
-                                      (unsigned long long)tv);
-                            atomicAdd((unsigned long long*)cnt,
-                                      (unsigned long long)tc);
-                        }
-                    } else if (tc) {
-                        if (q.agg_in_types[a] == BK_DOUBLE || at == BK_AGG_AVG)
-                            atomic_add_f64_global(val, td);
-                        else
-                            atomicAdd((unsigned long long*)val,
-                                      (unsigned long long)tv);
-                        atomicAdd((unsigned long long*)cnt,
-                                  (unsigned long long)tc);
-                    }
-                }
+                for (int off = 32; off > 0; off >>= 1)
+                    t = agg_part_join(q.aggs[a].agg_type, t,
+                                      agg_part_shfl<SHFL_XOR>(t, off));
+                if (lane == leader && slot)
+                    agg_part_fold<false>(slot, q, a, t);
             }
             pending &= ~mmask;
         }
@@ -1732,7 +1702,10 @@ __device__ __forceinline__ void agg_update_slot_rec(uint64_t* st, const BkQueryS
  * group (the common case inside a hot key's bucket — hash partitioning sends
  * a hot group's rows to one bucket, so its waves are single-key), butterfly-
  * reduce the agg inputs across the wave and issue ONE slot update instead of
- * 64 serialized same-address LDS atomics. Returns true if handled. */
+ * 64 serialized same-address LDS atomics. Returns true if handled.
+ * A partial per record, agg_part_join and agg_part_fold spelled out: through
+ * helpers k_part_agg is re-allocated (+-1 register) and the single-pass hash
+ * route measured ~0.1 % slower. Keep them in step. */
 __device__ __forceinline__ bool wave_combine_update(
         uint64_t* slot, const BkQuerySpec& q, const RecLayout& lay,
         const uint64_t* my, uint64_t meta, bool lds) {
@@ -2002,71 +1975,40 @@ __global__ void k_merge_blob(BkQuerySpec q, const uint32_t* flags, const uint64_
 struct SrcIdx { int32_t v[BK_MAX_AGGS]; };  /* level-1 agg index per level-2
                                                agg; -1 = synthesize from d */
 
-/* level-1 -> level-2 key plumbing: unpack the level-1 packed keys
- * (pack_group_keys layout: sequential shift packing with word overflow),
- * then REPACK the user keys per the level-2 spec's own declared widths —
- * the word splits can differ between the (keys + d) and keys-only
- * packings. eb = host-encoded bases. */
-struct RollK {
-    int32_t l1n;            /* level-1 key count (user keys + d), <= 3 */
-    int32_t l1bits[3];
-    uint64_t l1eb[3];
-    int32_t q2bits[2];
-    uint64_t q2eb[2];
-};
-
-/* Level-1 key layout for the rollup: with no declared group_bits the user
- * key sits raw in k0 and d raw in k1 (l1_bits* == 0). With declared bits
- * (the sort-dedup path REQUIRES this; the hash path then packs the same
- * way) both ride in k0: [d - base1 : bits1][key - base0 : bits0]; eb* are
- * the host-encoded bases, so the raw encodings are recovered here. */
+/* level-1 -> level-2 key plumbing: read each user key's full encoding out
+ * of the level-1 layout (user keys + d) and REPACK it per the level-2 spec's
+ * own layout (its widths and bases, the key words a direct GROUP BY with q2
+ * would produce). d is the last level-1 key. Packing is sequential, so a
+ * user key's word and shift are the same on both levels and the get-then-put
+ * never moves a field; it matters only where the two specs declare other
+ * widths or bases for the same key. Both layouts are kernel arguments:
+ * compile-time indices only. */
 __global__ void k_rollup(BkQuerySpec q2, int in_naggs, const uint64_t* in_table,
                          uint64_t in_nslots, uint64_t* out, uint64_t omask,
                          uint64_t fill_cap, uint64_t* fill, uint32_t* err,
-                         SrcIdx src, RollK rk) {
+                         SrcIdx src, BkKeyLayout l1, BkKeyLayout l2) {
     const int in_stride = SLOT_HDR + 2 * in_naggs;
     const int stride = SLOT_HDR + 2 * q2.n_aggs;
-    const int n_user = rk.l1n - 1;
+    const int n_user = l1.n - 1;
     uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t sl = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          sl < in_nslots; sl += gs) {
         const uint64_t* s = in_table + sl * in_stride;
         if (((const uint32_t*)s)[0] != 2u) continue;
         uint32_t f = ((const uint32_t*)s)[1];
-        /* unpack ALL level-1 keys (raw encodings; null -> 0) */
-        uint64_t e[3] = {0, 0, 0};
-        {
-            int shift = 0, word = 0;
-            for (int k = 0; k < rk.l1n; k++) {
-                int bits = rk.l1bits[k] ? rk.l1bits[k] : 64;
-                if (shift + bits > 64) { word++; shift = 0; }
-                uint64_t raw = (word == 0 ? s[1] : s[2]) >> shift;
-                if (bits < 64) raw &= (1ull << bits) - 1ull;
-                int isnull = (f >> (7 - k)) & 1;
-                e[k] = isnull ? 0 : (rk.l1bits[k] ? raw + rk.l1eb[k] : raw);
-                shift += bits;
-            }
+        uint64_t ok0 = 0, ok1 = 0, e_d = 0;
+        #pragma unroll
+        for (int k = 0; k < BK_MAX_GROUP; k++) {
+            if (k >= l1.n) break;
+            const uint64_t e = bk_key_get(&l1, k, s[1], s[2], f);
+            if (k == n_user) e_d = e;
+            else if (!((f >> (7 - k)) & 1)) bk_key_put(&l2, k, e, &ok0, &ok1);
         }
         int d_null = (f >> (7 - n_user)) & 1;
-        uint64_t e_d = e[n_user];
         uint64_t* g;
         if (q2.n_group == 0) {
             g = out;        /* out slot 0 pre-claimed */
         } else {
-            /* repack the user keys per the LEVEL-2 spec's widths (the
-             * layout a direct GROUP BY with q2 would produce) */
-            uint64_t ok0 = 0, ok1 = 0;
-            int shift = 0, word = 0;
-            for (int k = 0; k < n_user; k++) {
-                int bits = rk.q2bits[k] ? rk.q2bits[k] : 64;
-                if (shift + bits > 64) { word++; shift = 0; }
-                int isnull = (f >> (7 - k)) & 1;
-                uint64_t enc = isnull ? 0 : e[k];
-                if (!isnull && bits < 64)
-                    enc = (enc - rk.q2eb[k]) & ((1ull << bits) - 1ull);
-                if (word == 0) ok0 |= enc << shift; else ok1 |= enc << shift;
-                shift += bits;
-            }
             uint32_t uflag = f & (uint32_t)((0xFFu << (8 - n_user)) & 0xFFu);
             g = gtable_claim(out, omask, stride, uflag, ok0, ok1,
                              fill, fill_cap, err);
@@ -2074,63 +2016,22 @@ __global__ void k_rollup(BkQuerySpec q2, int in_naggs, const uint64_t* in_table,
         }
         const uint64_t* st_in = s + SLOT_HDR;
         for (int32_t a = 0; a < q2.n_aggs; a++) {
-            uint64_t* val = g + SLOT_HDR + 2 * a;
-            uint64_t* cnt = val + 1;
-            int at = q2.aggs[a].agg_type;
+            const int at = q2.aggs[a].agg_type;
+            AggPart p{0, 0, 0.0};
             if (at == BK_AGG_COUNT_DISTINCT) {
-                if (!d_null) atomicAdd((unsigned long long*)val, 1ull);
-                continue;
+                p.v = d_null ? 0 : 1;
+            } else if (at == BK_AGG_SUM_DISTINCT || at == BK_AGG_AVG_DISTINCT) {
+                /* the decoded dedup key is the one input */
+                p.v = (uint64_t)bk_dec_i64(e_d);
+                p.d = q2.agg_in_types[a] == BK_DOUBLE
+                          ? bk_dec_f64(e_d) : (double)bk_dec_i64(e_d);
+                p.c = d_null ? 0 : 1;
+            } else {
+                /* plain agg: additive merge of the matching level-1 state */
+                const int sa = src.v[a];
+                p = agg_part_of_state(st_in[2 * sa], st_in[2 * sa + 1]);
             }
-            if (at == BK_AGG_SUM_DISTINCT || at == BK_AGG_AVG_DISTINCT) {
-                if (!d_null) {
-                    if (q2.agg_in_types[a] == BK_DOUBLE ||
-                        at == BK_AGG_AVG_DISTINCT)
-                        atomic_add_f64_global(val,
-                            q2.agg_in_types[a] == BK_DOUBLE
-                                ? bk_dec_f64(e_d)
-                                : (double)bk_dec_i64(e_d));
-                    else
-                        atomicAdd((unsigned long long*)val,
-                                  (unsigned long long)(uint64_t)bk_dec_i64(e_d));
-                    atomicAdd((unsigned long long*)cnt, 1ull);
-                }
-                continue;
-            }
-            /* plain agg: additive merge of the matching level-1 state */
-            int sa = src.v[a];
-            uint64_t sv = st_in[2 * sa], sc = st_in[2 * sa + 1];
-            switch (at) {
-                case BK_AGG_COUNT_STAR:
-                case BK_AGG_COUNT:
-                    if (sv) atomicAdd((unsigned long long*)val,
-                                      (unsigned long long)sv);
-                    break;
-                case BK_AGG_SUM:
-                case BK_AGG_AVG:
-                    if (sc) {
-                        if (q2.agg_in_types[a] == BK_DOUBLE ||
-                            at == BK_AGG_AVG) {
-                            double d; memcpy(&d, &sv, 8);
-                            atomic_add_f64_global(val, d);
-                        } else {
-                            atomicAdd((unsigned long long*)val,
-                                      (unsigned long long)sv);
-                        }
-                        atomicAdd((unsigned long long*)cnt,
-                                  (unsigned long long)sc);
-                    }
-                    break;
-                case BK_AGG_MIN:
-                case BK_AGG_MAX:
-                    if (sc) {
-                        atomicMax((unsigned long long*)val,
-                                  (unsigned long long)sv);
-                        atomicAdd((unsigned long long*)cnt,
-                                  (unsigned long long)sc);
-                    }
-                    break;
-                default: break;
-            }
+            agg_part_fold<false>(g, q2, a, p);
         }
     }
 }
@@ -2923,18 +2824,6 @@ static int agg_compact(BkgAggOut* o) {
     return 0;
 }
 
-/* number of 64-bit key words the spec-packed group keys occupy */
-static int pack_key_words(const BkQuerySpec* q) {
-    if (q->n_group == 0) return 0;
-    int shift = 0, word = 0;
-    for (int32_t k = 0; k < q->n_group; k++) {
-        int bits = q->group_bits[k] ? q->group_bits[k] : 64;
-        if (shift + bits > 64) { word++; shift = 0; }
-        shift += bits;
-    }
-    return word + 1;
-}
-
 static bool any_group_bits(const BkQuerySpec* q) {
     for (int32_t k = 0; k < q->n_group; k++)
         if (q->group_bits[k]) return true;
@@ -2995,7 +2884,7 @@ static int build_rec_layout(BkgTable* t, const BkQuerySpec* q, RecLayout* lay) {
         lay->nwords = w;
         return 0;
     }
-    lay->k1_word = pack_key_words(q) >= 2 ? (k1_in_meta ? -2 : w++) : -1;
+    lay->k1_word = bk_key_layout(q).nwords >= 2 ? (k1_in_meta ? -2 : w++) : -1;
     bool need_meta = k1_in_meta || agg_meta;
     for (int k = 0; k < q->n_group; k++)
         if (t->valid[q->group_cols[k]]) need_meta = true;
@@ -3103,7 +2992,7 @@ static int query_exprs_check(const BkgTable* t, const BkQuerySpec* q) {
  * set. */
 static int query_shape_check(const BkgTable* t, const BkQuerySpec* q) {
     if (!t || !q) { set_err("null table or query spec"); return -1; }
-    if (pack_key_words(q) > 2) {
+    if (bk_key_layout(q).nwords > 2) {
         set_err("group keys exceed two packed 64-bit words "
                 "(set group_bits per key, bk_common.h)");
         return -1;
@@ -3759,24 +3648,9 @@ extern "C" BkgAggOut* bkgpu_agg_rollup(const BkgAggOut* in, const BkQuerySpec* q
         HIP_CHECK_NULL(hipMemcpy(ctr_host, in->ctrs, 24, hipMemcpyDeviceToHost));
         const_cast<BkgAggOut*>(in)->rows_passed = (int64_t)ctr_host[1];
     }
-    /* packed key layouts: per-key widths and ENCODED bases for the
-     * kernel's unpack (level 1: user keys + d) and repack (level 2) */
-    const BkQuerySpec& l1q = in->q;
-    RollK rk;
-    memset(&rk, 0, sizeof rk);
-    rk.l1n = l1q.n_group;
-    for (int k = 0; k < l1q.n_group && k < 3; k++) {
-        rk.l1bits[k] = l1q.group_bits[k];
-        rk.l1eb[k] = l1q.group_types[k] == BK_STRING
-                         ? (uint64_t)l1q.group_base[k]
-                         : bk_enc_i64(l1q.group_base[k]);
-    }
-    for (int k = 0; k < q2->n_group && k < 2; k++) {
-        rk.q2bits[k] = q2->group_bits[k];
-        rk.q2eb[k] = q2->group_types[k] == BK_STRING
-                         ? (uint64_t)q2->group_base[k]
-                         : bk_enc_i64(q2->group_base[k]);
-    }
+    /* packed key layouts for the kernel's unpack (level 1: user keys + d)
+     * and repack (level 2) */
+    const BkKeyLayout l1 = bk_key_layout(&in->q), l2 = bk_key_layout(q2);
     BkgAggOut* o = new BkgAggOut();
     o->q = *q2;
     int64_t nslots = next_pow2(std::max<int64_t>(expected_groups * 2, 1024));
@@ -3794,7 +3668,7 @@ extern "C" BkgAggOut* bkgpu_agg_rollup(const BkgAggOut* in, const BkQuerySpec* q
         hipLaunchKernelGGL(k_rollup, dim3(1024), dim3(256), 0, 0,
                            *q2, in->q.n_aggs, in->table, in->nslots,
                            o->table, o->nslots - 1, (o->nslots * 7) / 8,
-                           o->ctrs, o->err, src, rk);
+                           o->ctrs, o->err, src, l1, l2);
         tm.record();
         hipError_t lerr = hipGetLastError();
         if (lerr != hipSuccess) {
@@ -4091,32 +3965,6 @@ static int download_groups(BkgAggOut* o, HostGroups& hg) {
     return 0;
 }
 
-/* reverse of pack_group_keys: recover each key's full order-preserving
- * encoding from the two packed words (spec widths + bases) */
-static void unpack_group_keys(const BkQuerySpec& q, uint64_t k0, uint64_t k1,
-                              uint32_t flag, uint64_t* enc_out) {
-    int shift = 0, word = 0;
-    for (int32_t k = 0; k < q.n_group; k++) {
-        int bits = q.group_bits[k] ? q.group_bits[k] : 64;
-        if (shift + bits > 64) { word++; shift = 0; }
-        uint64_t w = word == 0 ? k0 : k1;
-        uint64_t e = 0;
-        if (!((flag >> (7 - k)) & 1)) {
-            if (bits == 64) {
-                e = w >> shift;   /* shift is 0 for a full word */
-            } else {
-                uint64_t eb = q.group_types[k] == BK_STRING
-                                  ? (uint64_t)q.group_base[k]
-                                  : bk_enc_i64(q.group_base[k]);
-                e = ((w >> shift) & ((1ull << bits) - 1)) + eb;
-            }
-        }
-        enc_out[k] = e;
-        shift += bits;
-    }
-    for (int32_t k = q.n_group; k < BK_MAX_GROUP; k++) enc_out[k] = 0;
-}
-
 extern "C" int64_t bkgpu_agg_fetch(BkgAggOut* o, int sorted, int64_t max_groups,
                                    uint8_t* flags, uint64_t* enc,
                                    int64_t* out_i, double* out_d, uint8_t* out_has) {
@@ -4127,10 +3975,12 @@ extern "C" int64_t bkgpu_agg_fetch(BkgAggOut* o, int sorted, int64_t max_groups,
     std::vector<int64_t> order(n);
     for (int64_t i = 0; i < n; i++) order[i] = i;
     /* recover per-key encodings (spec-packed keys, pack_group_keys) */
+    const BkKeyLayout kl = bk_key_layout(&o->q);
     std::vector<uint64_t> unp((size_t)(n > 0 ? n : 1) * BK_MAX_GROUP);
     for (int64_t i = 0; i < n; i++)
-        unpack_group_keys(o->q, hg.k0[i], hg.k1[i], hg.flags[i],
-                          unp.data() + (size_t)i * BK_MAX_GROUP);
+        for (int k = 0; k < kl.n; k++)
+            unp[(size_t)i * BK_MAX_GROUP + k] =
+                bk_key_get(&kl, k, hg.k0[i], hg.k1[i], hg.flags[i]);
     if (sorted) {
         const BkQuerySpec& q = o->q;
         std::sort(order.begin(), order.end(), [&](int64_t a, int64_t b) {
@@ -4157,34 +4007,11 @@ extern "C" int64_t bkgpu_agg_fetch(BkgAggOut* o, int sorted, int64_t max_groups,
             int64_t idx = (int64_t)a * out_n + i;
             int at = o->q.aggs[a].agg_type;
             int vt = o->q.agg_in_types[a];
-            out_i[idx] = 0; out_d[idx] = 0.0; out_has[idx] = 0;
-            switch (at) {
-                case BK_AGG_COUNT_STAR:
-                case BK_AGG_COUNT:
-                case BK_AGG_COUNT_DISTINCT:  /* COUNT-shaped state */
-                    out_i[idx] = (int64_t)val; out_has[idx] = 1; break;
-                case BK_AGG_SUM_DISTINCT:    /* SUM-shaped state */
-                case BK_AGG_SUM:
-                    if (!cnt) break;
-                    if (vt == BK_DOUBLE) memcpy(&out_d[idx], &val, 8);
-                    else out_i[idx] = (int64_t)val;
-                    out_has[idx] = 1; break;
-                case BK_AGG_AVG:
-                case BK_AGG_AVG_DISTINCT:
-                    if (!cnt) break;
-                    { double s; memcpy(&s, &val, 8); out_d[idx] = s / (double)cnt; }
-                    out_has[idx] = 1; break;
-                case BK_AGG_MIN:
-                case BK_AGG_MAX: {
-                    if (!cnt) break;
-                    uint64_t e = (at == BK_AGG_MIN) ? ~val : val;
-                    if (vt == BK_DOUBLE) out_d[idx] = bk_dec_f64(e);
-                    else if (vt == BK_STRING) out_i[idx] = (int64_t)(uint32_t)e;
-                    else out_i[idx] = bk_dec_i64(e);
-                    out_has[idx] = 1; break;
-                }
-                default: break;
-            }
+            uint64_t bits64;
+            out_has[idx] = (uint8_t)bk_agg_finalize(at, vt, val, cnt, &bits64);
+            out_i[idx] = 0; out_d[idx] = 0.0;
+            if (bk_agg_out_type(at, vt) == BK_DOUBLE) memcpy(&out_d[idx], &bits64, 8);
+            else out_i[idx] = (int64_t)bits64;
         }
     }
     return out_n;

@@ -8,20 +8,16 @@
 // table, dense arrays, sort-dedup table, scalar slot 0) settles into it, so
 // nothing here is per-form:
 //   [ flags: u32 * c ][ k0: u64 * c ][ k1: u64 * c ][ states: u64 * c*2*naggs ]
-// Finalization restates bkgpu_agg_fetch (agg_fn_call.cpp:927-975) and the
-// key decode of AggNode::get_next (agg_node.cpp:548-573) on the device.
+// Keys and states are read with the helpers bkgpu_agg_fetch uses
+// (bk_keylayout.h: bk_key_get, bk_agg_finalize), so the two cannot drift.
 
 #define POST_MAX_COLS (BK_MAX_GROUP + BK_MAX_AGGS)
 
 /* by-value kernel arguments: walked ONLY with compile-time indices inside
  * fully unrolled loops (no runtime indexing into kernarg-resident arrays,
  * DESIGN §4/§6) */
-struct PostKeys {
-    int32_t  bits[BK_MAX_GROUP];      /* declared width, 64 = full word */
-    int32_t  type[BK_MAX_GROUP];      /* OUTPUT column type */
-    uint64_t base_enc[BK_MAX_GROUP];  /* encoding of the declared base */
-};
-struct PostAggs {
+struct PostTypes {
+    int32_t key_type[BK_MAX_GROUP];   /* OUTPUT column type of each key */
     int32_t agg_type[BK_MAX_AGGS];
     int32_t in_type[BK_MAX_AGGS];
 };
@@ -51,7 +47,7 @@ k_agg_finalize(const uint32_t* __restrict__ flags,
                const uint64_t* __restrict__ k1,
                const uint64_t* __restrict__ states,
                const uint32_t* __restrict__ perm, int64_t n,
-               int n_group, int n_aggs, PostKeys pk, PostAggs pa, PostCols pc,
+               int n_aggs, BkKeyLayout kl, PostTypes pt, PostCols pc,
                uint32_t* nullmask) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     const bool live = i < n;
@@ -59,38 +55,21 @@ k_agg_finalize(const uint32_t* __restrict__ flags,
     uint32_t seen = 0;
     uint32_t flag = 0;
     uint64_t w0 = 0, w1 = 0;
-    if (live && n_group > 0) { flag = flags[g]; w0 = k0[g]; w1 = k1[g]; }
+    if (live && kl.n > 0) { flag = flags[g]; w0 = k0[g]; w1 = k1[g]; }
 
-    /* group keys: unpack_group_keys restated (spec widths + bases, null bit
-     * flags >> (7-k)), decoded as AggNode::get_next does */
-    int shift = 0, word = 0;
+    /* group keys, decoded as AggNode::get_next does */
     #pragma unroll
     for (int k = 0; k < BK_MAX_GROUP; k++) {
-        if (k < n_group) {
-            const int bits = pk.bits[k];
-            if (shift + bits > 64) { word++; shift = 0; }
-            const uint64_t w = word == 0 ? w0 : w1;
+        if (k < kl.n) {
             const bool has = !((flag >> (7 - k)) & 1);
-            uint64_t e;
-            if (bits == 64) e = w >> shift;   /* shift is 0 for a full word */
-            else e = ((w >> shift) & ((1ull << bits) - 1)) + pk.base_enc[k];
-            shift += bits;
-            const int32_t ty = pk.type[k];
-            uint64_t out;
-            if (ty == BK_DOUBLE) {
-                double d = bk_dec_f64(e);
-                __builtin_memcpy(&out, &d, 8);
-            } else if (ty == BK_STRING) {
-                out = (uint64_t)(uint32_t)e;
-            } else {
-                out = (uint64_t)bk_dec_i64(e);
-            }
+            const int32_t ty = pt.key_type[k];
+            const uint64_t out =
+                bk_enc_to_cell(ty, bk_key_get(&kl, k, w0, w1, flag));
             if (post_store(pc.data[k], pc.valid[k], ty, i, live, has, out))
                 seen |= 1u << k;
         }
     }
 
-    /* aggregates: the finalize switch of bkgpu_agg_fetch restated */
     #pragma unroll
     for (int a = 0; a < BK_MAX_AGGS; a++) {
         if (a < n_aggs) {
@@ -101,51 +80,12 @@ k_agg_finalize(const uint32_t* __restrict__ flags,
                 val = s[0];
                 cnt = s[1];
             }
-            const int at = pa.agg_type[a];
-            const int vt = pa.in_type[a];
-            bool has = false;
-            uint64_t out = 0;
-            int32_t ty = BK_INT64;
-            switch (at) {
-                case BK_AGG_COUNT_STAR:
-                case BK_AGG_COUNT:
-                case BK_AGG_COUNT_DISTINCT:  /* COUNT-shaped state */
-                    out = val; has = true; break;
-                case BK_AGG_SUM_DISTINCT:    /* SUM-shaped state */
-                case BK_AGG_SUM:
-                    ty = vt;
-                    if (!cnt) break;
-                    out = val; has = true; break;
-                case BK_AGG_AVG:
-                case BK_AGG_AVG_DISTINCT: {
-                    ty = BK_DOUBLE;
-                    if (!cnt) break;
-                    /* one IEEE f64 division, bit-identical to the host's */
-                    double s;
-                    __builtin_memcpy(&s, &val, 8);
-                    double q = s / (double)cnt;
-                    __builtin_memcpy(&out, &q, 8);
-                    has = true; break;
-                }
-                case BK_AGG_MIN:
-                case BK_AGG_MAX: {
-                    ty = vt;
-                    if (!cnt) break;
-                    uint64_t e = (at == BK_AGG_MIN) ? ~val : val;
-                    if (vt == BK_DOUBLE) {
-                        double d = bk_dec_f64(e);
-                        __builtin_memcpy(&out, &d, 8);
-                    } else if (vt == BK_STRING) {
-                        out = (uint64_t)(uint32_t)e;
-                    } else {
-                        out = (uint64_t)bk_dec_i64(e);
-                    }
-                    has = true; break;
-                }
-                default: break;
-            }
+            uint64_t out;
+            const bool has = bk_agg_finalize(pt.agg_type[a], pt.in_type[a],
+                                             val, cnt, &out);
             if (post_store(pc.data[BK_MAX_GROUP + a], pc.valid[BK_MAX_GROUP + a],
-                           ty, i, live, has, out))
+                           bk_agg_out_type(pt.agg_type[a], pt.in_type[a]),
+                           i, live, has, out))
                 seen |= 1u << (BK_MAX_GROUP + a);
         }
     }
@@ -180,15 +120,7 @@ static uint32_t* post_canonical_perm(const BkgAggOut* o, double* t_ms) {
     const uint32_t* flags = (const uint32_t*)b;
     const uint64_t* kw[2] = {(const uint64_t*)(b + c * 4),
                              (const uint64_t*)(b + c * 12)};
-    /* key layout: the pack_group_keys walk */
-    int kshift[BK_MAX_GROUP], kword[BK_MAX_GROUP], kbits[BK_MAX_GROUP];
-    int shift = 0, word = 0;
-    for (int k = 0; k < q.n_group; k++) {
-        int bits = q.group_bits[k] ? q.group_bits[k] : 64;
-        if (shift + bits > 64) { word++; shift = 0; }
-        kshift[k] = shift; kword[k] = word; kbits[k] = bits;
-        shift += bits;
-    }
+    const BkKeyLayout kl = bk_key_layout(&q);
     uint32_t *pa = nullptr, *pb = nullptr;
     uint64_t *keys = nullptr, *keys_out = nullptr;
     void* rp_tmp = nullptr;
@@ -206,12 +138,11 @@ static uint32_t* post_canonical_perm(const BkgAggOut* o, double* t_ms) {
     double t0 = t_ms ? now_ms() : 0;
     for (int k = q.n_group - 1; ok && k >= -1; k--) {
         const bool fl = k < 0;
-        const int bits = fl ? 8 : kbits[k];
+        const int bits = fl ? 8 : kl.bits[k];
         hipLaunchKernelGGL(k_post_sortkey, dim3(blocks), dim3(256), 0, 0,
-                           flags, fl ? kw[0] : kw[kword[k]],
+                           flags, fl ? kw[0] : kw[kl.word[k]],
                            first ? (const uint32_t*)nullptr : pa, n,
-                           fl ? 0 : kshift[k],
-                           bits >= 64 ? ~0ull : (1ull << bits) - 1,
+                           fl ? 0 : kl.shift[k], bk_key_mask(bits),
                            fl ? -1 : 7 - k, keys);
         if (first)
             hipLaunchKernelGGL(k_iota, dim3(256), dim3(256), 0, 0, pa,
@@ -250,8 +181,8 @@ extern "C" BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src,
         return nullptr;
     }
     const bool timing = debug_timing();
-    PostKeys pk{};
-    PostAggs pa{};
+    const BkKeyLayout kl = bk_key_layout(&q);
+    PostTypes pt{};
     PostCols pc{};
     BkgTable* t = new BkgTable();
     t->ncols = q.n_group + q.n_aggs;
@@ -259,28 +190,17 @@ extern "C" BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src,
     int slot_of[POST_MAX_COLS];      /* table column -> PostCols slot */
     int src_col[POST_MAX_COLS];      /* dictionary source column, -1 none */
     for (int k = 0; k < q.n_group; k++) {
-        pk.bits[k] = q.group_bits[k] ? q.group_bits[k] : 64;
-        pk.type[k] = q.group_fns[k] ? BK_INT64 : q.group_types[k];
-        pk.base_enc[k] = q.group_types[k] == BK_STRING
-                             ? (uint64_t)q.group_base[k]
-                             : bk_enc_i64(q.group_base[k]);
-        t->specs[k].col_type = pk.type[k];
+        pt.key_type[k] = q.group_fns[k] ? BK_INT64 : q.group_types[k];
+        t->specs[k].col_type = pt.key_type[k];
         slot_of[k] = k;
         src_col[k] = q.group_cols[k];
     }
     for (int a = 0; a < q.n_aggs; a++) {
         const int at = q.aggs[a].agg_type, vt = q.agg_in_types[a];
-        pa.agg_type[a] = at;
-        pa.in_type[a] = vt;
-        int32_t ot;    /* agg_out_type (bkexec.cpp) */
-        switch (at) {
-            case BK_AGG_COUNT_STAR: case BK_AGG_COUNT:
-            case BK_AGG_COUNT_DISTINCT: ot = BK_INT64; break;
-            case BK_AGG_AVG: case BK_AGG_AVG_DISTINCT: ot = BK_DOUBLE; break;
-            default: ot = vt; break;
-        }
+        pt.agg_type[a] = at;
+        pt.in_type[a] = vt;
         const int col = q.n_group + a;
-        t->specs[col].col_type = ot;
+        t->specs[col].col_type = bk_agg_out_type(at, vt);
         slot_of[col] = BK_MAX_GROUP + a;
         src_col[col] = ((at == BK_AGG_MIN || at == BK_AGG_MAX) &&
                         q.aggs[a].prog_len == 0) ? q.aggs[a].col : -1;
@@ -297,9 +217,7 @@ extern "C" BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src,
         /* every table column carries the 16-byte tail pad (cell_i64) */
         ok = hipMalloc(&t->data[col], (size_t)n * es + 16) == hipSuccess;
         const bool count_shaped = col >= q.n_group &&
-            (pa.agg_type[col - q.n_group] == BK_AGG_COUNT_STAR ||
-             pa.agg_type[col - q.n_group] == BK_AGG_COUNT ||
-             pa.agg_type[col - q.n_group] == BK_AGG_COUNT_DISTINCT);
+            bk_agg_count_shaped(pt.agg_type[col - q.n_group]);
         if (ok && !count_shaped && n > 0)
             ok = hipMalloc((void**)&t->valid[col], (size_t)n) == hipSuccess;
         if (!ok) set_err("agg_to_table: hipMalloc column failed");
@@ -321,8 +239,8 @@ extern "C" BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src,
                                (const uint32_t*)b, (const uint64_t*)(b + c * 4),
                                (const uint64_t*)(b + c * 12),
                                (const uint64_t*)(b + c * 20),
-                               (const uint32_t*)perm, n, (int)q.n_group,
-                               (int)q.n_aggs, pk, pa, pc, d_mask);
+                               (const uint32_t*)perm, n, (int)q.n_aggs,
+                               kl, pt, pc, d_mask);
             ok = hipGetLastError() == hipSuccess &&
                  hipMemcpy(&h_mask, d_mask, 4, hipMemcpyDeviceToHost) == hipSuccess;
             if (!ok) set_err("agg_to_table: finalize kernel failed");

@@ -554,3 +554,44 @@ def test_gpu_distinct_two_keys_with_nullable_key(eng, orc):
     assert np.array_equal(got["flags"], exp["flags"])
     assert np.array_equal(got["enc"], exp["enc"])
     assert np.array_equal(got["agg_i"], exp["agg_i"])
+
+
+@pytest.mark.gpu
+def test_gpu_distinct_rollup_level1_spills_to_second_word(eng, orc):
+    """Level 1 is [40, 20, 12] over (k0, k1, d): k0 and k1 fill 60 bits of
+    word 0, so d does not fit and sits alone in word 1; level 2 [40, 20]
+    keeps both user keys in word 0. k_rollup reads all three keys through
+    the level-1 layout and repacks the user keys through the level-2 one.
+    k1 has a negative base and NULLs, d has NULLs."""
+    from baikaldb_amd import QueryPlan
+    specs = [(TYPE_INT64, D_UNI, 0, 40, 0),            # k0
+             (TYPE_INT64, D_UNI, -12, 13, 100_000),    # k1, base -12, nullable
+             (TYPE_INT64, D_UNI, 0, 3000, 100_000),    # d (nullable)
+             (TYPE_INT64, D_UNI, 0, 1000, 0)]          # plain agg input
+    aggs = [("count_star", -1), ("count_distinct", 2), ("sum", 3),
+            ("sum_distinct", 2)]
+    conj = [(3, "<", 900)]
+    group = [0, 1]
+    n = 20_000
+    kw = dict(group_bits=[40, 20], group_base=[0, -12],
+              distinct_bits=12, distinct_base=0)
+    t = eng.create_table(specs, n)
+    try:
+        eng.generate(t, SEED + 2)
+        plan = QueryPlan(t.col_types, conjuncts=conj, group=group, aggs=aggs,
+                         **kw)
+        res = eng.filter_agg_distinct(t, plan, expected_l1_groups=1 << 15,
+                                      expected_groups=1 << 11)
+        try:
+            got = res.fetch(sorted=True)
+        finally:
+            res.free()
+    finally:
+        t.free()
+    exp, _ = oracle_distinct(orc, specs, n, conj, group, aggs, seed=SEED + 2,
+                             **kw)
+    assert got["ngroups"] == exp["ngroups"] > 1000
+    assert np.array_equal(got["flags"], exp["flags"])
+    assert np.array_equal(got["enc"], exp["enc"])
+    assert np.array_equal(got["agg_i"], exp["agg_i"])
+    assert np.array_equal(got["agg_has"], exp["agg_has"])

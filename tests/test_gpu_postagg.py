@@ -3,8 +3,8 @@
 # as sort_topk, window functions, re-aggregation, derive_expr.
 #
 # Section 1 compares to_table with the SAME engine's fetch(sorted=True): the
-# finalize kernel restates that host code, so every cell must be bit-equal
-# (AVG included - one IEEE division on both sides). Sections 2-4 compare with
+# finalize kernel and that host code share bk_keylayout.h, so every cell must
+# be bit-equal (AVG included - one IEEE division on both sides). Sections 2-4 compare with
 # an independent reference: the CPU oracle's filter_agg over the whole row
 # range (canonical order) with HAVING / ORDER BY / LIMIT / window /
 # re-aggregation applied in numpy, stable sorts so ties fall in canonical
@@ -27,7 +27,7 @@ gpu = pytest.mark.gpu
 
 # ---- helpers ----------------------------------------------------------------
 def out_type(ct, name, col):
-    """agg_out_type (bkexec.cpp): COUNT* -> INT64, AVG -> DOUBLE, SUM/MIN/MAX
+    """bk_agg_out_type (bk_keylayout.h): COUNT* -> INT64, AVG -> DOUBLE, SUM/MIN/MAX
     keep the input domain"""
     if name in ("count_star", "count", "count_distinct"):
         return I64
