@@ -13,15 +13,15 @@
 /* (ds-atomics at lidx = did - bucket_base): no hashing, no probe or   */
 /* claim chains, no generation flushes — the levers DESIGN.md §6 names */
 /* as the k_part_agg latency bound. The global result is a dense array */
-/* too (per-slot {touched, value words}), converted into the standard  */
-/* hash-table format at the end (k_dense_to_table) so compact / merge  */
-/* / rollup / fetch are untouched.                                     */
+/* too (per-slot {touched, value words}): k_dcompact turns it straight */
+/* into the wire blob, and dense_to_hash rebuilds a hash table from    */
+/* that blob only when merge / rollup need one.                        */
 /*                                                                     */
 /* Semantics identical to the hash path (same per-agg atomic op set,   */
 /* agg_node.cpp:405-587 / agg_fn_call.cpp:496-830): COUNT/SUM int64    */
 /* bit-exact (wrapping adds), SUM/AVG double within the stated         */
 /* tolerance (order-free f64 atomics), MIN/MAX exact on the order-     */
-/* preserving encoding. Eligibility (dense_eligible): 1-2 fn-free      */
+/* preserving encoding. Eligibility (dense_spans):    1-2 fn-free      */
 /* non-nullable group keys, no declared group_bits, non-nullable       */
 /* aggregate inputs (per-agg non-null counts == per-group row count,   */
 /* synthesized from one `touched` counter — 4x fewer atomics).         */
@@ -70,7 +70,7 @@ struct DRecLayout {
 
 struct DDesc { uint32_t bucket; uint32_t cnt; uint64_t start; };
 
-/* dense id of row r (keys verified non-null by dense_eligible) */
+/* dense id of row r (keys verified non-null by dense_spans) */
 template <bool SIMPLE>
 __device__ __forceinline__ uint32_t dense_did(const DevCols& cols,
                                               const BkQuerySpec& q,
@@ -917,7 +917,7 @@ __global__ void k_dcount(const uint64_t* gtouch, uint64_t span,
  * table is never built on this path): keys reconstruct from the dense id,
  * per-agg states synthesize exactly as agg_update_slot would have built
  * them — COUNT values and non-null counts are the touched counter
- * (dense_eligible guarantees non-nullable inputs). */
+ * (dense_spans guarantees non-nullable inputs). */
 __global__ void k_dcompact(BkQuerySpec q, DenseSpec ds, const uint64_t* gvals,
                            const uint64_t* gtouch, uint64_t* counter,
                            uint32_t* out_flags, uint64_t* out_k0,
@@ -958,13 +958,46 @@ static int ceil_log2_u64(uint64_t x) {
     return b;
 }
 
-/* Eligibility + plan: dense ids must fit BK_DENSE_MAX (default 2^23) and
- * every key / aggregate input must be non-nullable (counts synthesize from
- * `touched`). Returns false (ds/lay left undefined) otherwise. */
-static bool dense_eligible(BkgTable* t, const BkQuerySpec* q, DenseSpec* ds,
-                           DRecLayout* lay) {
-    if (const char* e = getenv("BK_DENSE"))
-        if (atoi(e) == 0) return false;
+typedef decltype(&k_dhisto<512, false, false, 0>) DHistoFn;
+typedef decltype(&k_dscatter<512, false>) DScatFn;
+typedef decltype(&k_dscatter_e<512, 1, 0, 0, false>) DScatEFn;
+typedef decltype(&k_dagg<1024, 1>) DAggFn;
+
+/* launch plan of the dense route (run_dense), fixed once per call like the
+ * hash route's PartPlan. Every knob of the route is read in dense_plan (and
+ * the helpers it calls once each) and nowhere else. */
+struct DensePlan {
+    int pref;                   /* BK_DENSE: 0 never; below 1 the sorted path
+                                 * goes first (sorted_first) */
+    DenseSpec ds;
+    DRecLayout lay;             /* final: PACK32 split decided */
+    bool simple;
+    BkQuerySpec qpad;
+    const BkQuerySpec* qk;      /* SIMPLE: the padded copy (points into this
+                                 * plan: plans are not copied) */
+    int nblocks, threads;       /* histo + scatter grid and block shape */
+    uint32_t nch;               /* OFFS_CHUNK tiles of the per-block counts */
+    DHistoFn histo_fn;
+    DScatFn scat_fn;            /* masked scatter, when no eager plan holds */
+    DScatEFn scat_e, scat_abs;  /* eager scatter, its absorbing twin, or null */
+    DScatE eprm;
+    DAggFn dagg_fn;
+    size_t histo_lds, scat_lds, abs_lds, dagg_lds;
+    bool dabs_on;               /* BK_DABS: chunks may absorb a hot bucket... */
+    double dabs_min;            /* ...holding this share of their survivors */
+    size_t abs_win;             /* dense ids per bucket = absorb window */
+    int pipe;                   /* BK_DPIPE in 1..4; 0 = unset (by size) */
+    uint64_t dagg_chunk;        /* records per dagg descriptor; 0 = by count */
+    uint32_t dagg_grid;         /* dagg grid cap */
+    DensePlan() = default;
+    DensePlan(const DensePlan&) = delete;
+};
+
+/* Eligibility and id spans: 1-2 fn-free non-nullable keys whose dense ids
+ * fit BK_DENSE_MAX (default 2^23), and non-nullable plain aggregate inputs
+ * (counts synthesize from `touched`). */
+static bool dense_spans(BkgTable* t, const BkQuerySpec* q, DenseSpec* ds,
+                        uint64_t* span_out) {
     if (q->n_group < 1 || q->n_group > 2) return false;
     if (any_group_bits(q)) return false;
     for (int32_t k = 0; k < q->n_group; k++) {
@@ -984,38 +1017,36 @@ static bool dense_eligible(BkgTable* t, const BkQuerySpec* q, DenseSpec* ds,
             (q->aggs[a].col2 < 0 || t->valid[q->aggs[a].col2]))
             return false;
     }
-    int c0 = q->group_cols[0];
-    if (ensure_stats(t, c0) != 0 || !t->stat_ok[c0] ||
-        t->stat_max[c0] < t->stat_min[c0])
-        return false;
-    uint64_t span0 = t->stat_max[c0] - t->stat_min[c0];
     uint64_t cap = 1ull << 23;
     if (const char* e = getenv("BK_DENSE_MAX")) cap = (uint64_t)atoll(e);
-    if (span0 >= cap) return false;
-    ds->base0 = t->stat_min[c0];
-    ds->base1 = 0;
-    ds->k1bits = 0;
-    if (q->n_group == 2) {
-        int c1 = q->group_cols[1];
-        if (ensure_stats(t, c1) != 0 || !t->stat_ok[c1] ||
-            t->stat_max[c1] < t->stat_min[c1])
+    uint64_t kspan[2] = {0, 0};
+    for (int32_t k = 0; k < q->n_group; k++) {
+        int c = q->group_cols[k];
+        if (ensure_stats(t, c) != 0 || !t->stat_ok[c] ||
+            t->stat_max[c] < t->stat_min[c])
             return false;
-        uint64_t span1 = t->stat_max[c1] - t->stat_min[c1];
-        if (span1 >= cap) return false;
-        ds->k1bits = (uint32_t)ceil_log2_u64(span1 + 1);
-        ds->base1 = t->stat_min[c1];
+        kspan[k] = t->stat_max[c] - t->stat_min[c];
+        if (kspan[k] >= cap) return false;
     }
-    uint64_t span = (span0 + 1) << ds->k1bits;
+    const bool two = q->n_group == 2;
+    ds->base0 = t->stat_min[q->group_cols[0]];
+    ds->base1 = two ? t->stat_min[q->group_cols[1]] : 0;
+    ds->k1bits = two ? (uint32_t)ceil_log2_u64(kspan[1] + 1) : 0;
+    uint64_t span = (kspan[0] + 1) << ds->k1bits;
     if (ds->k1bits >= 24 || span > cap) return false;
     ds->span = (uint32_t)span;
+    *span_out = span;
+    return true;
+}
 
-    /* record layout: narrow u32 deltas for int64-ish inputs whose span
-     * fits, wide u64 otherwise; u32 fields first (did at offset 0), pad,
-     * then 8-byte-aligned wide fields */
+/* record layout (unsplit) and ds's value slots: narrow u32 deltas for
+ * int64-ish inputs whose span fits, wide u64 otherwise; u32 fields first (did
+ * at offset 0), pad, then 8-byte-aligned wide fields. False past 8 words. */
+static bool dense_rec_layout(BkgTable* t, const BkQuerySpec* q, DenseSpec* ds,
+                             DRecLayout* lay) {
     int nv = 0;
-    int nnarrow = 0, nwide = 0;
-    lay->pk = 0;                               /* split layout decided later
-                                                  (run_dense, eager only) */
+    int nwide = 0;
+    lay->pk = 0;                               /* dense_pack32 may split it */
     int kind[BK_MAX_AGGS];                     /* 0 none, 1 narrow, 2 wide */
     for (int32_t a = 0; a < q->n_aggs; a++) {
         int at = q->aggs[a].agg_type;
@@ -1036,13 +1067,9 @@ static bool dense_eligible(BkgTable* t, const BkQuerySpec* q, DenseSpec* ds,
                 narrow = true;
                 /* SUM accumulates values, MIN/MAX accumulate encodings —
                  * both spans equal the encoding span (monotonic) */
-                vbase = at == BK_AGG_SUM
-                            ? (uint64_t)(int64_t)(t->stat_min[col]
-                                                  ^ (q->agg_in_types[a] ==
-                                                             BK_STRING
-                                                         ? 0
-                                                         : 1ull << 63))
-                            : t->stat_min[col];
+                const uint64_t sign =
+                    q->agg_in_types[a] == BK_STRING ? 0 : 1ull << 63;
+                vbase = t->stat_min[col] ^ (at == BK_AGG_SUM ? sign : 0);
             }
         }
         kind[a] = narrow ? 1 : 2;
@@ -1052,7 +1079,7 @@ static bool dense_eligible(BkgTable* t, const BkQuerySpec* q, DenseSpec* ds,
                       : is_f64                               ? 1
                                                              : 0;
         nv++;
-        if (narrow) nnarrow++; else nwide++;
+        if (!narrow) nwide++;
     }
     ds->nv = nv;
     int off = 1;                               /* u32 slot 0 = did */
@@ -1062,45 +1089,33 @@ static bool dense_eligible(BkgTable* t, const BkQuerySpec* q, DenseSpec* ds,
     for (int32_t a = 0; a < q->n_aggs; a++)
         if (kind[a] == 2) { lay->off32[a] = off; lay->wide[a] = 1; off += 2; }
     lay->nwords = (off + 1) / 2;
-    if (lay->nwords > 8) return false;
+    return lay->nwords <= 8;
+}
 
-    /* bucket granularity: largest power-of-2 slots/bucket whose LDS carve
-     * (nv u64 values + u32 touched per slot) fits 64 KB — 2 dagg blocks/CU
-     * (and headroom for a co-resident scatter block in the pipelined run);
-     * BK_DAGG_SHIFT overrides. */
+/* bucket granularity: largest power-of-2 slots/bucket whose LDS carve
+ * (nv u64 values + u32 touched per slot) fits 64 KB — 2 dagg blocks/CU
+ * (and headroom for a co-resident scatter block in the pipelined run);
+ * BK_DAGG_SHIFT overrides. False past 4096 buckets (histo arrays). */
+static bool dense_bucket_shift(DenseSpec* ds, uint64_t span) {
+    const size_t slot = 8 * (size_t)ds->nv + 4;
     uint32_t shift = 14;
-    while (shift > 0 &&
-           ((size_t)(1u << shift) * (8 * (size_t)nv + 4)) > 64 * 1024)
-        shift--;
+    while (shift > 0 && (size_t)(1u << shift) * slot > 64 * 1024) shift--;
     if (const char* e = getenv("BK_DAGG_SHIFT")) {
         int v = atoi(e);
-        if (v >= 6 && v <= 14 &&
-            ((size_t)(1u << v) * (8 * (size_t)nv + 4)) <= 144 * 1024)
+        if (v >= 6 && v <= 14 && (size_t)(1u << v) * slot <= 144 * 1024)
             shift = (uint32_t)v;
     }
     ds->shift = shift;
     ds->P = (uint32_t)((span + (1ull << shift) - 1) >> shift);
-    if (ds->P > 4096) return false;            /* bucketless histo arrays */
     ds->hshift = ds->shift >= ds->k1bits ? ds->shift - ds->k1bits
                                          : 0xFFFFFFFFu;
-    return true;
+    return ds->P <= 4096;
 }
 
-typedef void (*DHistoFn)(DevCols, BkQuerySpec, DenseSpec, int64_t, int64_t,
-                         uint16_t*, uint32_t*, uint64_t*);
-typedef void (*DScatFn)(DevCols, BkQuerySpec, DenseSpec, DRecLayout, int64_t,
-                        int64_t, const uint16_t*, const uint32_t*, uint64_t*);
-typedef void (*DScatEFn)(DevCols, BkQuerySpec, DenseSpec, DRecLayout, DScatE,
-                         int64_t, int64_t, const uint16_t*, const uint32_t*,
-                         uint64_t*, uint32_t*, uint32_t, uint64_t*,
-                         uint32_t*);
-
 /* classify the record fields for the eager scatter; false => masked path */
-static bool dense_eager_plan(const BkgTable* t, const DevCols& dc,
-                             const BkQuerySpec* q, const DenseSpec& ds,
-                             const DRecLayout& lay, DScatE* prm, int* nar_out,
-                             int* nf_out) {
-    if (getenv("BK_NO_DEAGER")) return false;
+static bool dense_eager_plan(const DevCols& dc, const BkQuerySpec* q,
+                             const DenseSpec& ds, const DRecLayout& lay,
+                             DScatE* prm, int* nar_out, int* nf_out) {
     int nar = 0, nf = 0;
     constexpr int WMAX = 3, NMAX = 2;
     for (int32_t k = 0; k < q->n_group; k++) {
@@ -1180,28 +1195,60 @@ static DScatEFn pick_dscat_e(int nk, int nar, int nf, bool abs_,
     return nullptr;
 }
 
-static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
-                     const DenseSpec& ds0, const DRecLayout& lay,
-                     int64_t row_begin, int64_t row_end) {
-    DenseSpec ds = ds0;
-    int64_t range = row_end - row_begin;
-    if (range >= (int64_t)UINT32_MAX * DPART_T) {
-        set_err("dense range too large");
-        return -1;
+/* PACK32 split records (see DRecLayout): possible when did bits + every
+ * narrow field's stats bits fit one u32 (stats are exact min/max, so field
+ * deltas provably fit). Fills the pk fields of lay; false leaves it unsplit.
+ * MEASURED-DEAD as default (DESIGN.md: 17.51 ms packed vs 16.60 ms AoS, the
+ * scatter is store-latency-bound, not byte-bound). BK_DREC_PACK=1 opts in;
+ * parity tests force it. */
+static bool dense_pack32(const BkgTable* t, const DenseSpec& ds,
+                         const DScatE& eprm, int nar, int nf, DRecLayout* lay) {
+    int bits[2] = {0, 0};
+    int tot = 0;
+    for (int i = 0; i < nar; i++) {
+        int col = eprm.ncol[i];
+        if (!t->stat_ok[col]) return false;
+        bits[i] = ceil_log2_u64(t->stat_max[col] - t->stat_min[col] + 1);
+        tot += bits[i];
     }
-    int nblocks = 4096;
-    if (const char* e = getenv("BK_DPART_BLOCKS")) nblocks = atoi(e);
-    const int threads = 512;
+    if (ceil_log2_u64(ds.span) + tot > 32) return false;
+    lay->pk = 1;
+    lay->pknf = nf;
+    lay->pkdidsh = (uint32_t)tot;
+    lay->pksh[0] = nar == 2 ? (uint32_t)bits[1] : 0;
+    lay->pksh[1] = 0;
+    for (int i = 0; i < 2; i++)
+        lay->pkmask[i] = bits[i] >= 32 ? 0xFFFFFFFFu : ((1u << bits[i]) - 1u);
+    return true;
+}
+
+/* false for a shape the dense route does not take (plan left undefined) */
+static bool dense_plan(DensePlan* pl, BkgTable* t, const BkQuerySpec* q) {
+    pl->pref = 1;
+    if (const char* e = getenv("BK_DENSE")) pl->pref = atoi(e);
+    if (pl->pref == 0) return false;
+    DenseSpec& ds = pl->ds;
+    uint64_t span = 0;
+    if (!dense_spans(t, q, &ds, &span) ||
+        !dense_rec_layout(t, q, &ds, &pl->lay) ||
+        !dense_bucket_shift(&ds, span))
+        return false;
+
+    pl->nblocks = 4096;
+    if (const char* e = getenv("BK_DPART_BLOCKS")) pl->nblocks = atoi(e);
+    if (pl->nblocks < 1) pl->nblocks = 4096;    /* no zero-block launch */
+    pl->nch = (uint32_t)((pl->nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK);
+    pl->threads = 512;
     DevCols dc = table_cols(t);
 
-    bool simple = query_simple(t, q) && getenv("BK_NO_SIMPLE") == nullptr;
-    BkQuerySpec qpad;
-    const BkQuerySpec* qk = q;
-    if (simple) { qpad = pad_simple_q(q); qk = &qpad; }
+    const bool simple = pl->simple =
+        query_simple(t, q) && getenv("BK_NO_SIMPLE") == nullptr;
+    pl->qk = q;
+    if (simple) { pl->qpad = pad_simple_q(q); pl->qk = &pl->qpad; }
     bool vec = simple;
     if (vec)
         for (int j = 0; j < 4; j++)
-            if (dc.c[qpad.conjuncts[j].col].lshift > 2) vec = false;
+            if (dc.c[pl->qpad.conjuncts[j].col].lshift > 2) vec = false;
     /* eager bucket keys: key col(s) vector-loadable */
     int kv = 0;
     if (vec) {
@@ -1219,7 +1266,7 @@ static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
      * the first two is exact; tail tiles still use the 4-padded
      * row_passes) */
     bool cj2 = q->n_conjuncts <= 2;
-    DHistoFn histo_fn =
+    pl->histo_fn =
         kv == 2  ? (cj2 ? k_dhisto<512, true, true, 2, 2>
                         : k_dhisto<512, true, true, 2, 4>)
         : kv == 1 ? (cj2 ? k_dhisto<512, true, true, 1, 2>
@@ -1228,301 +1275,206 @@ static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
                          : k_dhisto<512, true, true, 0, 4>)
         : simple  ? k_dhisto<512, true, false, 0>
                   : k_dhisto<512, false, false, 0>;
-    DScatFn scat_fn = simple ? k_dscatter<512, true>
-                             : k_dscatter<512, false>;
-    DScatE eprm;
-    memset(&eprm, 0, sizeof eprm);
-    int e_nar = 0, e_nf = 0;
-    DScatEFn scat_e = nullptr;
+    pl->scat_fn = simple ? k_dscatter<512, true> : k_dscatter<512, false>;
+    pl->histo_lds = 8 + (size_t)ds.P * 4;
+    pl->scat_lds = (size_t)ds.P * 4;
+
     /* eager scatter needs no SIMPLE query shape — the predicate was already
-     * settled into passbits; only the field classification matters */
-    if (dense_eager_plan(t, dc, q, ds, lay, &eprm, &e_nar, &e_nf))
-        scat_e = pick_dscat_e(q->n_group, e_nar, e_nf, false);
+     * settled into passbits; only the field classification matters.
+     * BK_NO_DEAGER keeps the masked scatter: no absorb, no PACK32 either. */
+    memset(&pl->eprm, 0, sizeof pl->eprm);
+    int nar = 0, nf = 0;
+    const bool eager = getenv("BK_NO_DEAGER") == nullptr &&
+                       dense_eager_plan(dc, q, ds, pl->lay, &pl->eprm, &nar, &nf);
+    pl->scat_e = eager ? pick_dscat_e(q->n_group, nar, nf, false) : nullptr;
+    pl->scat_abs = eager ? pick_dscat_e(q->n_group, nar, nf, true) : nullptr;
 
     /* hot-bucket absorption gate (per chunk; see k_dscatter_e ABS): the
      * measured per-bucket survivor histogram decides. LDS carve must fit
-     * beside the bucket cursors; threshold = fraction of chunk survivors
-     * the hottest bucket must hold to pay for the LDS reservation. */
-    /* MEASURED-DEAD default (config3 1e9, npipe=1, same box): absorbing the
-     * 39%-mass hot bucket moved dagg 3.78 -> 2.27 ms but the scatter paid
-     * 12.6 -> 16.0 ms — the absorb branch + ds-atomics inside the j-loop
-     * break the staged-load MLP the eager kernel lives on (same lesson as
-     * the padded-conjunct work: extra control flow in the hot loop costs
-     * more than the bytes it saves). Results are bit-identical either way;
-     * BK_DABS=1 opts in (and the parity tests force it). */
-    double dabs_min = 0.15;
-    if (const char* e = getenv("BK_DABS_MIN")) dabs_min = atof(e);
-    bool dabs_on = scat_e != nullptr && getenv("BK_DABS") &&
-                   atoi(getenv("BK_DABS")) != 0;
-    size_t abs_win = (size_t)1 << ds.shift;
-    size_t abs_lds = abs_win * (8 * (size_t)ds.nv + 4) + (size_t)ds.P * 4;
-    if (abs_lds > 144 * 1024) dabs_on = false;
+     * beside the bucket cursors; dabs_min = share of a chunk's survivors the
+     * hottest bucket must hold. MEASURED-DEAD as default (DESIGN.md: dagg
+     * 3.78 -> 2.27 ms, but the scatter pays 12.6 -> 16.0 ms); bit-identical
+     * either way; BK_DABS=1 opts in (and the parity tests force it). */
+    pl->dabs_min = 0.15;
+    if (const char* e = getenv("BK_DABS_MIN")) pl->dabs_min = atof(e);
+    pl->abs_win = (size_t)1 << ds.shift;
+    pl->dagg_lds = pl->abs_win * (8 * (size_t)ds.nv + 4);
+    pl->abs_lds = pl->dagg_lds + (size_t)ds.P * 4;
+    pl->dabs_on = pl->scat_e != nullptr && getenv("BK_DABS") &&
+                  atoi(getenv("BK_DABS")) != 0 && pl->abs_lds <= 144 * 1024;
 
-    /* PACK32 split records (see DRecLayout): eligible when the eager plan
-     * holds, ABS is off, and did bits + every narrow field's stats bits fit
-     * one u32 (stats are exact min/max, so field deltas provably fit).
-     * MEASURED-DEAD as default (config3 1e9, same box, parity identical):
-     * 17.51 ms packed vs 16.60 ms AoS — the 24->20 B saving splits the
-     * record into a scattered 4-B hdr store + a 16-B payload store, and the
-     * extra scattered dword stream costs more than the 4 B/record it saves
-     * (same lesson as 32-B padding: the scatter is store-latency-bound,
-     * not byte-bound). BK_DREC_PACK=1 opts in; parity tests force it. */
-    DRecLayout laye = lay;
-    if (scat_e && !dabs_on && getenv("BK_DREC_PACK") &&
-        atoi(getenv("BK_DREC_PACK")) != 0) {
-        int didbits = ceil_log2_u64(ds.span);
-        int bits[2] = {0, 0};
-        int tot = 0;
-        bool ok = true;
-        for (int i = 0; i < e_nar; i++) {
-            int col = eprm.ncol[i];
-            if (!t->stat_ok[col]) { ok = false; break; }
-            uint64_t span_i = t->stat_max[col] - t->stat_min[col];
-            bits[i] = ceil_log2_u64(span_i + 1);
-            tot += bits[i];
-        }
-        if (ok && didbits + tot <= 32) {
-            laye.pk = 1;
-            laye.pknf = e_nf;
-            laye.pkdidsh = (uint32_t)tot;
-            laye.pksh[0] = e_nar == 2 ? (uint32_t)bits[1] : 0;
-            laye.pksh[1] = 0;
-            for (int i = 0; i < 2; i++)
-                laye.pkmask[i] =
-                    bits[i] >= 32 ? 0xFFFFFFFFu : ((1u << bits[i]) - 1u);
-            scat_e = pick_dscat_e(q->n_group, e_nar, e_nf, false, true);
-        }
+    /* absorb takes precedence: with it on, every chunk — absorbing or not —
+     * runs the unsplit layout */
+    bool pk = pl->scat_e && !pl->dabs_on && getenv("BK_DREC_PACK") &&
+              atoi(getenv("BK_DREC_PACK")) != 0 &&
+              dense_pack32(t, ds, pl->eprm, nar, nf, &pl->lay);
+    if (pk) pl->scat_e = pick_dscat_e(q->n_group, nar, nf, false, true);
+
+    int dilp = 2;
+    if (const char* e = getenv("BK_DAGG_ILP")) dilp = atoi(e);
+    pl->dagg_fn = pk ? (dilp == 2 ? k_dagg<1024, 2, true>
+                                  : k_dagg<1024, 1, true>)
+                     : (dilp == 2 ? k_dagg<1024, 2> : k_dagg<1024, 1>);
+    pl->dagg_chunk = 0;
+    if (const char* e = getenv("BK_DAGG_CHUNK")) pl->dagg_chunk = (uint64_t)atoll(e);
+    pl->dagg_grid = 32768;
+    if (const char* e = getenv("BK_DAGG_GRID")) {
+        uint32_t g = (uint32_t)atoi(e);
+        if (g > 0 && g < pl->dagg_grid) pl->dagg_grid = g;
     }
+    pl->pipe = 0;
+    if (const char* e = getenv("BK_DPIPE"))
+        pl->pipe = std::min(4, std::max(1, atoi(e)));
+    return true;
+}
 
-    /* chunked 2-stream pipelining: chunk c's LDS-atomic-heavy dagg overlaps
-     * chunk c+1's HBM-bound histo/scatter. The dense accumulator arrays
-     * (gvals/gtouch) are SHARED — every op is an order-free atomic (adds /
-     * maxes), so results are identical to the single-pass run; one
-     * dense_to_table at the end converts the combined result. */
-    int npipe = range >= 400 * 1000 * 1000 ? 2 : 1;
-    if (const char* e = getenv("BK_DPIPE")) npipe = atoi(e);
-    if (npipe < 1) npipe = 1;
-    if (npipe > 4) npipe = 4;
-    hipStream_t* dstreams = nullptr;
-    if (npipe > 1 && !(dstreams = pipe_streams())) return -1;
-
-    const uint32_t P = ds.P;
-    const uint32_t nch = (nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK;
+/* Dense GROUP BY for one attempt; returns like run_partitioned, whose chunk
+ * scaffolding (bkgpu.hip) this loop shares. When piped, chunk c's
+ * LDS-atomic-heavy dagg overlaps chunk c+1's HBM-bound histo/scatter; the
+ * accumulators (gvals/gtouch) are SHARED — every op is an order-free atomic
+ * (adds / maxes), so results are identical to the single pass. */
+static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
+                     const DensePlan& pl, int64_t row_begin, int64_t row_end) {
+    const DenseSpec& ds = pl.ds;
+    const DRecLayout& lay = pl.lay;
+    int64_t range = row_end - row_begin;
+    if (range >= (int64_t)UINT32_MAX * DPART_T) {
+        set_err("dense range too large");
+        return -1;
+    }
+    int npipe = pl.pipe ? pl.pipe : range >= 400 * 1000 * 1000 ? 2 : 1;
+    ChunkSplit sp(row_begin, row_end, npipe);
+    if (sp.piped() && !sp.streams) return -1;
+    DevCols dc = table_cols(t);
+    const uint32_t P = ds.P, nch = pl.nch;
+    const int nblocks = pl.nblocks, threads = pl.threads;
     const uint64_t span_alloc = (uint64_t)P << ds.shift;
-    int64_t per = (range + npipe - 1) / npipe;
-    struct DSlot {
+
+    struct Slot : ChunkBufs {
         uint16_t* passbits = nullptr;
-        uint32_t *H = nullptr, *totals = nullptr, *base = nullptr,
-                 *S = nullptr;
-        uint64_t* total_dev = nullptr;
-        uint64_t* rec = nullptr;
         DDesc* ddesc = nullptr;
         uint64_t* vslab = nullptr;   /* ABS per-block hot-bucket slabs */
         uint32_t* tslab = nullptr;
+        void recycle() { ChunkBufs::recycle(); pool_free(ddesc); ddesc = nullptr; }
     } sl[2];
     uint64_t *gvals = nullptr, *gtouch = nullptr;
     auto cleanup = [&]() {
-        for (int i = 0; i < 2; i++) {
-            pool_free(sl[i].passbits); pool_free(sl[i].H);
-            pool_free(sl[i].totals); pool_free(sl[i].base); pool_free(sl[i].S);
-            pool_free(sl[i].total_dev); pool_free(sl[i].rec);
-            pool_free(sl[i].ddesc);
-            pool_free(sl[i].vslab); pool_free(sl[i].tslab);
+        for (Slot& s : sl) {
+            pool_free(s.passbits); pool_free(s.ddesc); pool_free(s.vslab);
+            pool_free(s.tslab); s.release();
         }
         pool_free(gvals); pool_free(gtouch);
     };
-    #define DCHECK(x) do { if ((x) != hipSuccess) { \
-        snprintf(g_err, sizeof g_err, "dense %s:%d %s", __FILE__, __LINE__, \
-                 hipGetErrorString(hipGetLastError())); \
-        (void)hipDeviceSynchronize(); cleanup(); return -1; } } while (0)
-    int nslots_used = npipe > 1 ? 2 : 1;
-    uint64_t per_tiles = (uint64_t)((per + DPART_T - 1) / DPART_T);
-    for (int i = 0; i < nslots_used; i++) {
-        DCHECK(pool_alloc((void**)&sl[i].passbits, per_tiles * 2 + 16));
-        DCHECK(pool_alloc((void**)&sl[i].H, (size_t)nblocks * P * 4));
-        DCHECK(pool_alloc((void**)&sl[i].totals, (size_t)P * 4));
-        DCHECK(pool_alloc((void**)&sl[i].base, (size_t)P * 4));
-        DCHECK(pool_alloc((void**)&sl[i].S, (size_t)nch * P * 4));
-        DCHECK(pool_alloc((void**)&sl[i].total_dev, 8));
+    uint64_t per_tiles = (uint64_t)((sp.per + DPART_T - 1) / DPART_T);
+    for (int i = 0; i < sp.nslots(); i++) {
+        CHK("dense", pool_alloc((void**)&sl[i].passbits, per_tiles * 2 + 16));
+        CHK("dense", sl[i].alloc_prefix(nblocks, P, nch));
     }
-    DCHECK(pool_alloc((void**)&gvals, (size_t)span_alloc * ds.nv * 8 + 8));
-    DCHECK(pool_alloc((void**)&gtouch, (size_t)span_alloc * 8));
-    DCHECK(hipMemset(gvals, 0, (size_t)span_alloc * ds.nv * 8 + 8));
-    DCHECK(hipMemset(gtouch, 0, (size_t)span_alloc * 8));
+    const size_t gvals_bytes = (size_t)span_alloc * ds.nv * 8 + 8;
+    CHK("dense", pool_alloc((void**)&gvals, gvals_bytes));
+    CHK("dense", pool_alloc((void**)&gtouch, (size_t)span_alloc * 8));
+    CHK("dense", hipMemset(gvals, 0, gvals_bytes));
+    CHK("dense", hipMemset(gtouch, 0, (size_t)span_alloc * 8));
 
     static const char* DNAMES[] = {"dhisto", "dtotals", "dscan", "doffs",
                                    "dscatter", "dagg", "dtotab"};
-    static const char* PNAMES[] = {"dpipe"};
-    size_t histo_lds = 8 + (size_t)P * 4;
-    size_t agg_lds = ((size_t)1 << ds.shift) * (8 * (size_t)ds.nv + 4);
-    uint64_t CH0 = 0;
-    if (const char* e = getenv("BK_DAGG_CHUNK")) CH0 = (uint64_t)atoll(e);
-
-    EvTimer tm;
-    double t0 = 0;
-    if (npipe == 1) tm.record();
-    else { DCHECK(hipDeviceSynchronize()); t0 = now_ms(); }
+    ChunkClock ck{sp};
+    CHK("dense", ck.start());
+    ck.mark();
     std::vector<DDesc> descs;
+    std::vector<uint32_t> h_tot(P), h_base(P);
     for (int c = 0; c < npipe; c++) {
-        int si = npipe > 1 ? (c & 1) : 0;
-        hipStream_t st = npipe > 1 ? dstreams[si] : 0;
-        int64_t cb = row_begin + (int64_t)c * per;
-        int64_t ce = cb + per < row_end ? cb + per : row_end;
-        if (ce <= cb) break;
-        if (c >= 2) {   /* recycle slot only after its chunk fully drained */
-            DCHECK(hipStreamSynchronize(st));
-            pool_free(sl[si].rec);
-            sl[si].rec = nullptr;
-            pool_free(sl[si].ddesc);
-            sl[si].ddesc = nullptr;
-        }
-        DCHECK(hipMemsetAsync(sl[si].totals, 0, (size_t)P * 4, st));
-        hipLaunchKernelGGL(histo_fn, dim3(nblocks), dim3(threads), histo_lds,
-                           st, dc, *qk, ds, cb, ce, sl[si].passbits, sl[si].H,
-                           o->ctrs + 1);
-        if (npipe == 1) tm.record();
-        hipLaunchKernelGGL(k_part_totals, dim3((P * nch + 255) / 256),
-                           dim3(256), 0, st, sl[si].H, nblocks, P, sl[si].S,
-                           sl[si].totals);
-        if (npipe == 1) tm.record();
-        hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, st,
-                           sl[si].totals, P, sl[si].base, sl[si].total_dev);
-        if (npipe == 1) tm.record();
-        DCHECK(hipGetLastError());
+        Chunk k;
+        CHK("dense", chunk_open(sp, c, sl, &k));
+        if (k.ce <= k.cb) break;
+        Slot& s = sl[k.si];
+        hipStream_t st = k.st;
+        CHK("dense", hipMemsetAsync(s.totals, 0, (size_t)P * 4, st));
+        hipLaunchKernelGGL(pl.histo_fn, dim3(nblocks), dim3(threads),
+                           pl.histo_lds, st, dc, *pl.qk, ds, k.cb, k.ce,
+                           s.passbits, s.H, o->ctrs + 1);
+        ck.mark();
         uint64_t total = 0;
-        std::vector<uint32_t> h_tot(P), h_base(P);
-        DCHECK(hipMemcpyAsync(&total, sl[si].total_dev, 8,
-                              hipMemcpyDeviceToHost, st));
-        DCHECK(hipMemcpyAsync(h_tot.data(), sl[si].totals, (size_t)P * 4,
-                              hipMemcpyDeviceToHost, st));
-        DCHECK(hipMemcpyAsync(h_base.data(), sl[si].base, (size_t)P * 4,
-                              hipMemcpyDeviceToHost, st));
-        DCHECK(hipStreamSynchronize(st));   /* other stream keeps running */
-        hipLaunchKernelGGL(k_part_offsets, dim3((P * nch + 255) / 256),
-                           dim3(256), 0, st, sl[si].H, nblocks, P,
-                           sl[si].base, sl[si].S);
-        if (npipe == 1) tm.record();
-        /* hottest bucket of THIS chunk (exact measured counts) */
-        uint32_t hotb = 0;
-        uint64_t hotn = 0;
-        if (dabs_on && total > 0)
-            for (uint32_t b = 0; b < P; b++)
-                if (h_tot[b] > hotn) { hotn = h_tot[b]; hotb = b; }
-        bool absorb = dabs_on && total > 0 &&
-                      hotn >= (uint64_t)(dabs_min * (double)total);
+        CHK("dense", prefix_pass(s, nblocks, P, nch, st, ck, &total,
+                                 h_tot.data(), h_base.data()));
+        /* hottest bucket of THIS chunk (measured counts; first of equals) */
+        const uint32_t hotb = (uint32_t)(
+            std::max_element(h_tot.begin(), h_tot.end()) - h_tot.begin());
+        bool absorb = pl.dabs_on && total > 0 &&
+                      h_tot[hotb] >= (uint64_t)(pl.dabs_min * (double)total);
         uint32_t* hdrp = nullptr;
         if (total > 0) {
-            size_t rec_bytes = laye.pk
-                ? (size_t)total * ((size_t)laye.pknf * 8 + 4) + 8
+            size_t rec_bytes = lay.pk
+                ? (size_t)total * ((size_t)lay.pknf * 8 + 4) + 8
                 : (size_t)total * lay.nwords * 8;
-            DCHECK(pool_alloc((void**)&sl[si].rec, rec_bytes));
-            if (laye.pk)
-                hdrp = (uint32_t*)(sl[si].rec + (size_t)total * laye.pknf);
+            CHK("dense", pool_alloc((void**)&s.rec, rec_bytes));
+            if (lay.pk) hdrp = (uint32_t*)(s.rec + (size_t)total * lay.pknf);
             if (absorb) {
-                if (!sl[si].vslab && ds.nv > 0)
-                    DCHECK(pool_alloc((void**)&sl[si].vslab,
-                                      (size_t)nblocks * abs_win * ds.nv * 8));
-                if (!sl[si].tslab)
-                    DCHECK(pool_alloc((void**)&sl[si].tslab,
-                                      (size_t)nblocks * abs_win * 4));
-                DScatEFn scat_a =
-                    pick_dscat_e(q->n_group, e_nar, e_nf, true);
-                hipLaunchKernelGGL(scat_a, dim3(nblocks), dim3(threads),
-                                   abs_lds, st,
-                                   dc, *qk, ds, lay, eprm, cb, ce,
-                                   sl[si].passbits, sl[si].H, sl[si].rec,
-                                   nullptr, hotb << ds.shift, sl[si].vslab,
-                                   sl[si].tslab);
-                hipLaunchKernelGGL(k_dabs_reduce, dim3(256), dim3(256), 0,
-                                   st, ds, hotb << ds.shift,
-                                   (uint32_t)nblocks, sl[si].vslab,
-                                   sl[si].tslab, gvals, gtouch);
-            } else if (scat_e)
-                hipLaunchKernelGGL(scat_e, dim3(nblocks), dim3(threads),
-                                   (size_t)P * 4, st,
-                                   dc, *qk, ds, laye, eprm, cb, ce,
-                                   sl[si].passbits, sl[si].H, sl[si].rec,
+                const size_t slab = (size_t)nblocks * pl.abs_win;
+                if (!s.vslab && ds.nv > 0)
+                    CHK("dense", pool_alloc((void**)&s.vslab, slab * ds.nv * 8));
+                if (!s.tslab)
+                    CHK("dense", pool_alloc((void**)&s.tslab, slab * 4));
+                hipLaunchKernelGGL(pl.scat_abs, dim3(nblocks), dim3(threads),
+                                   pl.abs_lds, st, dc, *pl.qk, ds, lay,
+                                   pl.eprm, k.cb, k.ce, s.passbits, s.H, s.rec,
+                                   nullptr, hotb << ds.shift, s.vslab, s.tslab);
+                hipLaunchKernelGGL(k_dabs_reduce, dim3(256), dim3(256), 0, st,
+                                   ds, hotb << ds.shift, (uint32_t)nblocks,
+                                   s.vslab, s.tslab, gvals, gtouch);
+            } else if (pl.scat_e)
+                hipLaunchKernelGGL(pl.scat_e, dim3(nblocks), dim3(threads),
+                                   pl.scat_lds, st, dc, *pl.qk, ds, lay,
+                                   pl.eprm, k.cb, k.ce, s.passbits, s.H, s.rec,
                                    hdrp, 0u, nullptr, nullptr);
             else
-                hipLaunchKernelGGL(scat_fn, dim3(nblocks), dim3(threads),
-                                   (size_t)P * 4, st,
-                                   dc, *qk, ds, lay, cb, ce, sl[si].passbits,
-                                   sl[si].H, sl[si].rec);
+                hipLaunchKernelGGL(pl.scat_fn, dim3(nblocks), dim3(threads),
+                                   pl.scat_lds, st, dc, *pl.qk, ds, lay, k.cb,
+                                   k.ce, s.passbits, s.H, s.rec);
         }
-        if (npipe == 1) tm.record();
+        ck.mark();
         /* descriptors: per bucket, runs of <= CH records (balances skewed
          * range buckets); flush traffic = ndesc x live slots */
-        uint64_t CH = CH0 ? CH0 : std::max<uint64_t>(65536, total / 768);
+        uint64_t CH = pl.dagg_chunk ? pl.dagg_chunk
+                                    : std::max<uint64_t>(65536, total / 768);
         descs.clear();
         for (uint32_t b = 0; b < P; b++) {
-            if (absorb && b == hotb) continue;   /* absorbed in-scatter:
-                                                    its records were never
-                                                    written */
+            if (absorb && b == hotb) continue;   /* records never written */
             uint64_t n = h_tot[b], s0 = h_base[b];
-            for (uint64_t ofs = 0; ofs < n; ofs += CH) {
-                DDesc d;
-                d.bucket = b;
-                d.cnt = (uint32_t)std::min<uint64_t>(CH, n - ofs);
-                d.start = s0 + ofs;
-                descs.push_back(d);
-            }
+            for (uint64_t ofs = 0; ofs < n; ofs += CH)
+                descs.push_back({b, (uint32_t)std::min<uint64_t>(CH, n - ofs),
+                                 s0 + ofs});
         }
         if (total > 0 && !descs.empty()) {
-            DCHECK(pool_alloc((void**)&sl[si].ddesc,
-                              descs.size() * sizeof(DDesc)));
-            DCHECK(hipMemcpyAsync(sl[si].ddesc, descs.data(),
-                                  descs.size() * sizeof(DDesc),
-                                  hipMemcpyHostToDevice, st));
-            uint32_t grid = (uint32_t)std::min<size_t>(descs.size(), 32768);
-            if (const char* e = getenv("BK_DAGG_GRID")) {
-                uint32_t g = (uint32_t)atoi(e);
-                if (g > 0 && g < grid) grid = g;
-            }
-            int dilp = 2;
-            if (const char* e = getenv("BK_DAGG_ILP")) dilp = atoi(e);
-            auto dagg_fn =
-                laye.pk
-                    ? (dilp == 2 ? k_dagg<1024, 2, true>
-                                 : k_dagg<1024, 1, true>)
-                    : (dilp == 2 ? k_dagg<1024, 2> : k_dagg<1024, 1>);
-            hipLaunchKernelGGL(dagg_fn, dim3(grid), dim3(1024), agg_lds,
-                               st, *q, ds, laye, sl[si].rec, hdrp,
-                               sl[si].ddesc, (uint32_t)descs.size(), gvals,
-                               gtouch);
+            const size_t dbytes = descs.size() * sizeof(DDesc);
+            CHK("dense", pool_alloc((void**)&s.ddesc, dbytes));
+            CHK("dense", hipMemcpyAsync(s.ddesc, descs.data(), dbytes,
+                                        hipMemcpyHostToDevice, st));
+            uint32_t grid =
+                (uint32_t)std::min<size_t>(descs.size(), pl.dagg_grid);
+            hipLaunchKernelGGL(pl.dagg_fn, dim3(grid), dim3(1024), pl.dagg_lds,
+                               st, *q, ds, lay, s.rec, hdrp, s.ddesc,
+                               (uint32_t)descs.size(), gvals, gtouch);
         }
-        if (npipe == 1) tm.record();
-        DCHECK(hipGetLastError());
+        ck.mark();
+        CHK("dense", hipGetLastError());
     }
-    if (npipe > 1) {
-        DCHECK(hipStreamSynchronize(dstreams[0]));
-        DCHECK(hipStreamSynchronize(dstreams[1]));
-    }
-    if (npipe == 1) {
-        tm.record();
-        tm.finish(o, DNAMES);
-    } else {
-        DCHECK(hipDeviceSynchronize());
-        double wall = now_ms() - t0;
-        o->kernel_ms = (float)wall;
-        o->n_kernels = 1;
-        o->t_ms[0] = (float)wall;
-        snprintf(o->k_names[0], 16, "%s", PNAMES[0]);
-    }
+    ck.mark();                      /* "dtotab": nothing left to convert */
+    CHK("dense", ck.finish(o, DNAMES, "dpipe"));
     /* adopt the dense result: compact reads these arrays directly; the
      * hash table (16-slot stub) is rebuilt lazily by dense_to_hash only
      * if merge/rollup need slot probing */
-    if (o->dvals) pool_free(o->dvals);
-    if (o->dtouch) pool_free(o->dtouch);
+    pool_free(o->dvals);
+    pool_free(o->dtouch);
     o->dvals = gvals;
     o->dtouch = gtouch;
     gvals = gtouch = nullptr;
-    DenseSpec* sp = (DenseSpec*)malloc(sizeof(DenseSpec));
-    *sp = ds;
+    DenseSpec* spec = (DenseSpec*)malloc(sizeof(DenseSpec));
+    *spec = ds;
     free(o->dense_spec);
-    o->dense_spec = sp;
+    o->dense_spec = spec;
     o->dense_mode = true;
     cleanup();
-    #undef DCHECK
     return 0;
 }
 

@@ -3072,16 +3072,9 @@ static BkQuerySpec pad_simple_q(const BkQuerySpec* q) {
  * count that has no instantiation falls to 256. HOT only when the adaptive
  * lock-on is enabled (BK_HOT_MIN <= 4096); default is the lean no-table
  * variant. */
-typedef void (*HistoFn)(DevCols, BkQuerySpec, int64_t, int64_t, uint32_t,
-                        uint16_t*, uint32_t*, uint64_t*, uint64_t, uint64_t,
-                        uint64_t*, uint64_t*, uint32_t*, uint32_t, uint32_t,
-                        uint32_t, uint32_t);
-typedef void (*ScatFn)(DevCols, BkQuerySpec, RecLayout, int64_t, int64_t,
-                       uint32_t, const uint16_t*, const uint32_t*, uint64_t*,
-                       uint64_t, int);
-typedef void (*PartAggFn)(BkQuerySpec, RecLayout, const uint64_t*, uint64_t,
-                          uint64_t, uint64_t*, uint64_t, uint64_t, uint64_t*,
-                          uint32_t*, uint32_t);
+typedef decltype(&k_part_histo<256, false>) HistoFn;
+typedef decltype(&k_part_scatter<256>) ScatFn;
+typedef decltype(&k_part_agg<256, 1>) PartAggFn;
 static HistoFn pick_histo(int threads, bool hot, bool simple) {
     if (simple && !hot) {
         if (threads == 512)  return k_part_histo<512, false, true>;
@@ -3108,6 +3101,124 @@ static PartAggFn pick_part_agg(int threads, int ilp) {
     if (threads == 1024)
         return ilp == 2 ? k_part_agg<1024, 2> : k_part_agg<1024, 1>;
     return ilp == 2 ? k_part_agg<256, 2> : k_part_agg<256, 1>;
+}
+
+/* ---- chunk scaffolding of the two partition routes: run_partitioned (hash
+ * buckets, below) and run_dense (range buckets, bkdpart.inc) are one loop —
+ * per row chunk a histogram, the prefix pass, a scatter and an aggregate,
+ * chunks alternating between two streams and buffer slots when piped ---- */
+
+/* a failed step ends the call: report the status THAT step returned (not the
+ * last-error slot), then drain the device before the caller's cleanup()
+ * hands buffers back — the pool is not stream-aware */
+#define CHK(route, x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { \
+    snprintf(g_err, sizeof g_err, route " %s:%d %s", __FILE__, __LINE__, \
+             hipGetErrorString(e_)); \
+    (void)hipGetLastError(); \
+    (void)hipDeviceSynchronize(); cleanup(); return -1; } } while (0)
+
+/* row split of one call: npipe chunks of `per` rows; the single pass is the
+ * one-chunk case on the null stream */
+struct ChunkSplit {
+    int64_t row_begin, row_end, per;
+    int npipe;
+    hipStream_t* streams;       /* the pipe_streams() pair when piped; null
+                                 * with the last error set: give up */
+    ChunkSplit(int64_t rb, int64_t re, int n)
+        : row_begin(rb), row_end(re), per((re - rb + n - 1) / n), npipe(n),
+          streams(n > 1 ? pipe_streams() : nullptr) {}
+    bool piped() const { return npipe > 1; }
+    int nslots() const { return piped() ? 2 : 1; }
+};
+
+/* per-slot buffers both routes have: per-block bucket counts and their prefix
+ * arrays (sized once per call), the chunk's records (sized per chunk). A
+ * route's slot derives from this and adds its own. */
+struct ChunkBufs {
+    uint32_t *H = nullptr, *totals = nullptr, *base = nullptr, *S = nullptr;
+    uint64_t *total_dev = nullptr, *rec = nullptr;
+    hipError_t alloc_prefix(int nblocks, uint32_t P, uint32_t nch) {
+        hipError_t e = pool_alloc((void**)&H, (size_t)nblocks * P * 4);
+        if (!e) e = pool_alloc((void**)&totals, (size_t)P * 4);
+        if (!e) e = pool_alloc((void**)&base, (size_t)P * 4);
+        if (!e) e = pool_alloc((void**)&S, (size_t)nch * P * 4);
+        if (!e) e = pool_alloc((void**)&total_dev, 8);
+        return e;
+    }
+    void recycle() { pool_free(rec); rec = nullptr; }   /* per-chunk part */
+    void release() {
+        pool_free(H); pool_free(totals); pool_free(base); pool_free(S);
+        pool_free(total_dev); pool_free(rec);
+    }
+};
+
+/* chunk c: rows [cb, ce) (empty: past the end, stop), slot and stream. A slot
+ * comes round again two chunks later; its stream drains before its per-chunk
+ * buffers (Slot::recycle) return to the pool. */
+struct Chunk { int64_t cb, ce; int si; hipStream_t st; };
+template <class Slot>
+static hipError_t chunk_open(const ChunkSplit& sp, int c, Slot* sl, Chunk* k) {
+    k->si = sp.piped() ? (c & 1) : 0;
+    k->st = sp.piped() ? sp.streams[k->si] : 0;
+    k->cb = sp.row_begin + (int64_t)c * sp.per;
+    k->ce = std::min(k->cb + sp.per, sp.row_end);
+    if (c < 2 || k->ce <= k->cb) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(k->st);
+    if (!e) sl[k->si].recycle();
+    return e;
+}
+
+/* timing: per-kernel events in the single pass (mark() after each launch),
+ * one wall-clock entry when piped (the two streams' kernels overlap) */
+struct ChunkClock {
+    const ChunkSplit& sp;
+    EvTimer tm;
+    double t0 = 0;
+    hipError_t start() {
+        hipError_t e = sp.piped() ? hipDeviceSynchronize() : hipSuccess;
+        t0 = now_ms();
+        return e;
+    }
+    void mark() { if (!sp.piped()) tm.record(); }
+    /* waits for the last kernel either way */
+    hipError_t finish(BkgAggOut* o, const char* const* names,
+                      const char* wall_name) {
+        if (!sp.piped()) { tm.finish(o, names); return hipSuccess; }
+        hipError_t e = hipStreamSynchronize(sp.streams[0]);
+        if (!e) e = hipStreamSynchronize(sp.streams[1]);
+        o->kernel_ms = o->t_ms[0] = (float)(now_ms() - t0);
+        o->n_kernels = 1;
+        snprintf(o->k_names[0], 16, "%s", wall_name);
+        return e;
+    }
+};
+
+/* between a chunk's histogram (H[block][bucket] counts) and its scatter:
+ * bucket totals, their exclusive scan, per-block start offsets. The records
+ * are sized from the chunk total, so the host waits for this chunk's stream
+ * here (the other keeps running); h_tot / h_base ride along in that wait. */
+static hipError_t prefix_pass(const ChunkBufs& b, int nblocks, uint32_t P,
+                              uint32_t nch, hipStream_t st, ChunkClock& ck,
+                              uint64_t* total, uint32_t* h_tot = nullptr,
+                              uint32_t* h_base = nullptr) {
+    const dim3 tiles((P * nch + 255) / 256);
+    hipLaunchKernelGGL(k_part_totals, tiles, dim3(256), 0, st, b.H, nblocks,
+                       P, b.S, b.totals);
+    ck.mark();
+    hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, st, b.totals, P,
+                       b.base, b.total_dev);
+    ck.mark();
+    const hipMemcpyKind D2H = hipMemcpyDeviceToHost;
+    hipError_t e = hipGetLastError();
+    if (!e) e = hipMemcpyAsync(total, b.total_dev, 8, D2H, st);
+    if (!e && h_tot) e = hipMemcpyAsync(h_tot, b.totals, (size_t)P * 4, D2H, st);
+    if (!e && h_base) e = hipMemcpyAsync(h_base, b.base, (size_t)P * 4, D2H, st);
+    if (!e) e = hipStreamSynchronize(st);
+    if (e) return e;
+    hipLaunchKernelGGL(k_part_offsets, tiles, dim3(256), 0, st, b.H, nblocks,
+                       P, b.base, b.S);
+    ck.mark();
+    return hipSuccess;
 }
 
 #include "bkdpart.inc"
@@ -3155,6 +3266,7 @@ static void part_plan(PartPlan* pl, BkgTable* t, const BkQuerySpec* q,
      * in-flight blocks are the only free-lunch lever left) */
     pl->nblocks = 8192;
     if (const char* e = getenv("BK_PART_BLOCKS")) pl->nblocks = atoi(e);
+    if (pl->nblocks < 1) pl->nblocks = 8192;    /* no zero-block launch */
     pl->nch = (uint32_t)((pl->nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK);
     /* histo+scatter MUST share grid AND block shape (H rows are per-block).
      * 512 threads measured best (histo 5.7->3.4 ms, scatter 9.9->8.3 ms at
@@ -3237,15 +3349,12 @@ static void part_plan(PartPlan* pl, BkgTable* t, const BkQuerySpec* q,
 }
 
 /* Hash-partitioned GROUP BY for one attempt; returns 0 ok (err flag still
- * to be checked by caller), -1 hard error. One loop over row chunks, as in
- * run_dense. Large ranges split into chunks that alternate between TWO HIP
- * streams, so one chunk's part_agg (LDS-latency-bound, ~1.2 TB/s — NOT
- * HBM-saturated) overlaps the next chunk's histo/scatter (HBM-bound). The
- * global table is shared — its claim protocol is already additive/concurrent
- * (same as inter-block claims), so results are identical to the single pass,
- * which is the one-chunk case on the null stream with per-kernel event
- * timing. Per-slot buffers are reused only after their stream synchronizes
- * (the pool is not stream-aware). */
+ * to be checked by caller), -1 hard error. One loop over row chunks on the
+ * scaffolding above. Large ranges pipe: one chunk's part_agg (LDS-latency-
+ * bound, ~1.2 TB/s — NOT HBM-saturated) overlaps the next chunk's
+ * histo/scatter (HBM-bound). The global table is shared — its claim protocol
+ * is already additive/concurrent (same as inter-block claims), so results
+ * are identical to the single pass. */
 static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
                            int64_t row_begin, int64_t row_end,
                            int64_t expected_groups) {
@@ -3256,106 +3365,66 @@ static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
                  expected_groups >= (1 << 20)) ? 2 : 1;
     if (pl.pipe >= 0) npipe = pl.pipe;
     if (npipe < 2 || range < (int64_t)4 * npipe) npipe = 1;
-    const bool piped = npipe > 1;
-    hipStream_t* streams = nullptr;
-    if (piped && !(streams = pipe_streams())) return -1;
-    const int64_t per = (range + npipe - 1) / npipe;
-    if (per >= (int64_t)UINT32_MAX) {
+    ChunkSplit sp(row_begin, row_end, npipe);
+    const bool piped = sp.piped();
+    if (piped && !sp.streams) return -1;
+    if (sp.per >= (int64_t)UINT32_MAX) {
         set_err("row chunk too large for one pass");
         return -1;
     }
     const uint32_t P = pl.P, nch = pl.nch;
     const int nblocks = pl.nblocks, threads = pl.threads;
 
-    struct Slot {
-        uint16_t* bucketid = nullptr;
-        uint32_t *H = nullptr, *totals = nullptr, *base = nullptr, *S = nullptr;
-        uint64_t* total_dev = nullptr;
-        uint64_t* rec = nullptr;
-    } sl[2];
+    struct Slot : ChunkBufs { uint16_t* bucketid = nullptr; } sl[2];
     auto cleanup = [&]() {
-        for (int i = 0; i < 2; i++) {
-            pool_free(sl[i].bucketid); pool_free(sl[i].H); pool_free(sl[i].totals);
-            pool_free(sl[i].base); pool_free(sl[i].S); pool_free(sl[i].total_dev);
-            pool_free(sl[i].rec);
-        }
+        for (Slot& s : sl) { pool_free(s.bucketid); s.release(); }
     };
-    /* the pool is not stream-aware: nothing goes back to it while a kernel
-     * may still write it */
-    #define PCHECK(x) do { if ((x) != hipSuccess) { \
-        snprintf(g_err, sizeof g_err, "part %s:%d %s", __FILE__, __LINE__, \
-                 hipGetErrorString(hipGetLastError())); \
-        (void)hipDeviceSynchronize(); cleanup(); return -1; } } while (0)
-    for (int i = 0; i < (piped ? 2 : 1); i++) {
-        PCHECK(pool_alloc((void**)&sl[i].bucketid, (size_t)per * 2));
-        PCHECK(pool_alloc((void**)&sl[i].H, (size_t)nblocks * P * 4));
-        PCHECK(pool_alloc((void**)&sl[i].totals, (size_t)P * 4));
-        PCHECK(pool_alloc((void**)&sl[i].base, (size_t)P * 4));
-        PCHECK(pool_alloc((void**)&sl[i].S, (size_t)nch * P * 4));
-        PCHECK(pool_alloc((void**)&sl[i].total_dev, 8));
+    for (int i = 0; i < sp.nslots(); i++) {
+        CHK("part", pool_alloc((void**)&sl[i].bucketid, (size_t)sp.per * 2));
+        CHK("part", sl[i].alloc_prefix(nblocks, P, nch));
     }
     DevCols dc = table_cols(t);
 
     static const char* NAMES[] = {"histo", "totals", "scan", "offsets",
                                   "scatter", "part_agg"};
-    EvTimer tm;
-    double t0 = 0;
-    if (piped) { PCHECK(hipDeviceSynchronize()); t0 = now_ms(); }
+    ChunkClock ck{sp};
+    CHK("part", ck.start());
     for (int c = 0; c < npipe; c++) {
-        Slot& s = sl[piped ? (c & 1) : 0];
-        hipStream_t st = piped ? streams[c & 1] : 0;
-        int64_t cb = row_begin + (int64_t)c * per;
-        int64_t ce = cb + per < row_end ? cb + per : row_end;
-        if (ce <= cb) break;
-        if (c >= 2) {
-            /* slot reuse: its previous chunk must be fully done before we
-             * recycle the record buffer */
-            PCHECK(hipStreamSynchronize(st));
-            pool_free(s.rec);
-            s.rec = nullptr;
-        }
-        PCHECK(hipMemsetAsync(s.totals, 0, (size_t)P * 4, st));
-        if (!piped) tm.record();
+        Chunk k;
+        CHK("part", chunk_open(sp, c, sl, &k));
+        if (k.ce <= k.cb) break;
+        Slot& s = sl[k.si];
+        hipStream_t st = k.st;
+        CHK("part", hipMemsetAsync(s.totals, 0, (size_t)P * 4, st));
+        ck.mark();
         hipLaunchKernelGGL(pl.histo_fn, dim3(nblocks), dim3(threads),
-                           pl.histo_lds, st,
-                           dc, *pl.qk, cb, ce, P, s.bucketid, s.H,
-                           o->table, o->nslots - 1, (o->nslots * 7) / 8,
-                           o->ctrs, o->ctrs + 1, o->err, pl.hot_slots,
-                           pl.hot_cap, pl.hot_probe, pl.hot_min);
-        if (!piped) tm.record();
-        hipLaunchKernelGGL(k_part_totals, dim3((P * nch + 255) / 256), dim3(256),
-                           0, st, s.H, nblocks, P, s.S, s.totals);
-        if (!piped) tm.record();
-        hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, st,
-                           s.totals, P, s.base, s.total_dev);
-        if (!piped) tm.record();
-        PCHECK(hipGetLastError());
+                           pl.histo_lds, st, dc, *pl.qk, k.cb, k.ce, P,
+                           s.bucketid, s.H, o->table, o->nslots - 1,
+                           (o->nslots * 7) / 8, o->ctrs, o->ctrs + 1, o->err,
+                           pl.hot_slots, pl.hot_cap, pl.hot_probe, pl.hot_min);
+        ck.mark();
         uint64_t total = 0;
-        PCHECK(hipMemcpyAsync(&total, s.total_dev, 8, hipMemcpyDeviceToHost, st));
-        PCHECK(hipStreamSynchronize(st));   /* other stream keeps running */
-        if (!piped && getenv("BK_DEBUG")) {
+        CHK("part", prefix_pass(s, nblocks, P, nch, st, ck, &total));
+        if (!piped && debug_timing()) {
             uint64_t passed = 0;
             (void)hipMemcpy(&passed, o->ctrs + 1, 8, hipMemcpyDeviceToHost);
             fprintf(stderr, "[bkgpu] passed=%llu cold_records=%llu hot_absorbed=%.1f%%\n",
                     (unsigned long long)passed, (unsigned long long)total,
                     passed ? 100.0 * (double)(passed - total) / (double)passed : 0.0);
         }
-        hipLaunchKernelGGL(k_part_offsets, dim3((P * nch + 255) / 256), dim3(256),
-                           0, st, s.H, nblocks, P, s.base, s.S);
-        if (!piped) tm.record();
         if (total > 0) {
-            PCHECK(pool_alloc((void**)&s.rec, (size_t)total * pl.lay.nwords * 8));
-            /* BK_PAIR is a single-pass experiment (part_plan: the stash
-             * costs the scatter its occupancy, a net loss); the two-stream
-             * form never pairs */
+            size_t rec_bytes = (size_t)total * pl.lay.nwords * 8;
+            CHK("part", pool_alloc((void**)&s.rec, rec_bytes));
+            /* BK_PAIR is a single-pass experiment (part_plan: a net loss);
+             * the two-stream form never pairs */
             size_t pair_lds = (size_t)P * pl.lay.nwords * 8 + (size_t)P * 8;
             int paired = !piped && pl.pair && pair_lds <= 130 * 1024;
             size_t sc_lds = paired ? pair_lds : (size_t)P * 8;
             hipLaunchKernelGGL(pl.scat_fn, dim3(nblocks), dim3(threads), sc_lds,
-                               st, dc, *pl.qk, pl.lay, cb, ce, P, s.bucketid,
+                               st, dc, *pl.qk, pl.lay, k.cb, k.ce, P, s.bucketid,
                                s.H, s.rec, total, paired);
         }
-        if (!piped) tm.record();
+        ck.mark();
         if (total > 0) {
             /* chunk ~ bucket size: fewer generation flushes (flush traffic ~
              * chunks x distinct-per-chunk), while >=2048 chunks keep the chip
@@ -3367,28 +3436,17 @@ static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
             uint32_t grid = (uint32_t)std::min<uint64_t>(
                 nrec_chunks, piped ? pl.pipe_agg_grid : 32768);
             hipLaunchKernelGGL(pl.agg_fn, dim3(grid), dim3(pl.at),
-                               pl.agg_lds_bytes, st,
-                               *q, pl.lay, s.rec, total, chunk,
-                               o->table, o->nslots - 1, (o->nslots * 7) / 8,
-                               o->ctrs, o->err, pl.agg_lds_slots);
+                               pl.agg_lds_bytes, st, *q, pl.lay, s.rec, total,
+                               chunk, o->table, o->nslots - 1,
+                               (o->nslots * 7) / 8, o->ctrs, o->err,
+                               pl.agg_lds_slots);
         }
-        if (!piped) tm.record();
-        PCHECK(hipGetLastError());
+        ck.mark();
+        CHK("part", hipGetLastError());
     }
     /* rows_passed is accumulated by k_part_histo (hot + cold alike) */
-    if (piped) {
-        PCHECK(hipStreamSynchronize(streams[0]));
-        PCHECK(hipStreamSynchronize(streams[1]));
-        double wall = now_ms() - t0;
-        o->kernel_ms = (float)wall;
-        o->n_kernels = 1;
-        o->t_ms[0] = (float)wall;
-        snprintf(o->k_names[0], 16, "pipeline");
-    } else {
-        tm.finish(o, NAMES);    /* waits for the last kernel */
-    }
+    CHK("part", ck.finish(o, NAMES, "pipeline"));
     cleanup();
-    #undef PCHECK
     return 0;
 }
 
@@ -3397,30 +3455,18 @@ static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
 #define FUSED_MAX_GROUPS 512
 
 /* Whether bkgpu_filter_agg tries the sort-dedup aggregate (bkdedup.inc) on a
- * partitioned shape before the dense / hash partition: for high-cardinality
- * GROUP BY and for small/mid row ranges where the partitioned pipeline's
- * fixed passes dominate.
- *
- * Sort-dedup routing, re-measured at round-2 close: the DENSE pipeline
- * now beats the sorted path at every plain-GROUP-BY size once a shape
- * is dense-eligible (c2a shape, same box: 3e7 rows 0.50 vs 1.25 ms,
- * 1e8 0.68 vs 1.63, 2e8 0.94 vs 2.21; at the 1e9 c2b EQ-selective
- * shape they tie, 3.018 vs 3.02) — the round-2 staged-load dense work
- * obsoleted the earlier "sorted ~3x faster at 1e8" measurement this
- * block was built on. Dense-eligible shapes therefore go dense
- * outright (BK_DENSE below 1 puts the sorted path first again); the
- * sorted path remains the route for shapes dense cannot
- * take (wide key spans, nullable keys) within its range caps, and the
- * designed path for high-cardinality DISTINCT level 1. An EQUALITY
- * conjunct still raises the sorted range bound for those shapes (the
- * reference's index selector uses the same signal,
- * src/physical_plan/index_selector.cpp), gated on a survivor estimate
- * from column stats. BK_SORTED_RANGE overrides (0 = off). */
+ * partitioned shape before the dense / hash partition. Never when the dense
+ * route goes first (`dense_first`: the shape is dense-eligible and the plan's
+ * BK_DENSE preference is >= 1 — dense beats the sorted path at every plain-
+ * GROUP-BY size). Otherwise the sorted path is the route for
+ * shapes dense cannot take (wide key spans, nullable keys) within its range
+ * caps, and the designed path for high-cardinality DISTINCT level 1. An
+ * EQUALITY conjunct raises the range bound (the reference's index selector
+ * uses the same signal, src/physical_plan/index_selector.cpp), gated on a
+ * survivor estimate from column stats. BK_SORTED_RANGE overrides (0 = off). */
 static bool sorted_first(BkgTable* t, const BkQuerySpec* q, int64_t row_begin,
-                         int64_t row_end, bool use_dense) {
-    int dense_pref = 1;
-    if (const char* e = getenv("BK_DENSE")) dense_pref = atoi(e);
-    if (use_dense && dense_pref >= 1) return false;
+                         int64_t row_end, bool dense_first) {
+    if (dense_first) return false;
     /* the raised cap applies only when the EQ plausibly SELECTS: a
      * low-selectivity EQ (2-valued column) over 1e9 rows would
      * materialize ~5e8 key/rowid records before falling back. Estimate
@@ -3535,15 +3581,14 @@ extern "C" BkgAggOut* bkgpu_filter_agg(BkgTable* t, const BkQuerySpec* q,
     bool partitioned = q->n_group > 0 && expected_groups > FUSED_MAX_GROUPS &&
                        row_end > row_begin;
 
-    /* dense-span plan (bkdpart.inc): a small packed key domain turns the
-     * aggregate into a range partition + direct-indexed LDS accumulate (no
-     * hash probes / claim chains). Preferred at large ranges; BK_DENSE=0
-     * disables, BK_DENSE=2 prefers it at every range. */
-    DenseSpec dsp;
-    DRecLayout dlay;
-    bool use_dense = partitioned && dense_eligible(t, q, &dsp, &dlay);
+    /* dense plan (bkdpart.inc): a small packed key domain turns the aggregate
+     * into a range partition + direct-indexed LDS accumulate (no hash probes
+     * / claim chains). BK_DENSE=0 disables it. */
+    DensePlan dpl;
+    bool use_dense = partitioned && dense_plan(&dpl, t, q);
 
-    if (partitioned && sorted_first(t, q, row_begin, row_end, use_dense)) {
+    if (partitioned &&
+        sorted_first(t, q, row_begin, row_end, use_dense && dpl.pref >= 1)) {
         BkgAggOut* so = bkgpu_filter_agg_sorted(t, q, row_begin, row_end);
         if (so) return so;
         g_err[0] = 0;   /* shape did not qualify — partitioned path */
@@ -3561,7 +3606,7 @@ extern "C" BkgAggOut* bkgpu_filter_agg(BkgTable* t, const BkQuerySpec* q,
         }
         if (debug_timing()) { (void)hipDeviceSynchronize(); t_alloc = now_ms(); }
         int rc = use_dense
-            ? run_dense(o, t, q, dsp, dlay, row_begin, row_end)
+            ? run_dense(o, t, q, dpl, row_begin, row_end)
             : partitioned
                 ? run_partitioned(o, t, q, row_begin, row_end, expected_groups)
                 : run_fused(o, t, q, row_begin, row_end, expected_groups);

@@ -1,6 +1,6 @@
 # Dense-span partition pipeline (bkdpart.inc) parity tests: BK_DENSE=2
 # forces the dense path wherever eligible, so these shapes exercise
-# k_dhisto / k_dscatter / k_dagg / k_dense_to_table directly and compare
+# k_dhisto / k_dscatter / k_dagg / k_dcompact directly and compare
 # against the CPU oracle (same seeded inputs, bk_datagen.h on both sides).
 # Reference semantics under test: hash aggregate agg_node.cpp:405-587 +
 # AggFnCall update/merge agg_fn_call.cpp:496-830 — results must be

@@ -144,7 +144,7 @@ def whole(world, monkeypatch, sh, rb=0, re_=None):
 
 
 def eligible(sh, route):
-    """dense routes need dense_eligible(); every shape here passes
+    """dense routes need dense_plan(); every shape here passes
     filter_agg_sorted (auto-packed or 24 declared bits - never >= 25)"""
     return route not in ("DENSE", "DPIPE") or sh.dense
 
@@ -645,7 +645,7 @@ class DShape:
         return self.name
 
 
-# nullable d runs k_rollup's d_null path; dense_eligible() refuses nullable
+# nullable d runs k_rollup's d_null path; dense_plan() refuses nullable
 # keys, so the dense + dense form has a sibling shape with d NOT NULL
 D_KEY = DShape("d_key", [0], 150_000)
 D_NOKEY = DShape("d_nokey", [], 150_000)

@@ -106,7 +106,7 @@ class Shape:
         self.name, self.specs, self.conj = name, specs, conj
         self.group, self.aggs, self.n, self.eg = group, aggs, n, eg
         self.bits, self.base = bits, base
-        self.dense = dense           # dense_eligible() accepts it
+        self.dense = dense           # dense_plan() accepts it
         self.ct = [s[0] for s in specs]
 
     def clone(self, name, **kw):
@@ -563,7 +563,7 @@ def test_dense_pipelined_tiny(world, monkeypatch):
 
 
 # nv = 3 (S6), 6 (S5), 2 (S3_F2): (1 << 10) * (8 * nv + 4) <= 52 KB, inside
-# dense_eligible's 144 KB guard, so shifts 6 and 10 are both accepted; at
+# dense_plan's 144 KB guard, so shifts 6 and 10 are both accepted; at
 # shift 6 the ~1e5-id spans give 1563 / 2000 buckets (<= 4096)
 DAGG = [dict(BK_DAGG_CHUNK=1000), dict(BK_DAGG_GRID=1), dict(BK_DAGG_ILP=1),
         dict(BK_DAGG_SHIFT=6), dict(BK_DAGG_SHIFT=10),
@@ -618,6 +618,62 @@ def test_dense_optins_under_pipelining(world, monkeypatch, sh, g):
               rng=(1, sh.n))
     run_route(world, monkeypatch, sh, kn(base, BK_DPIPE=3), DPIPE,
               rng=(7, sh.n - 3))
+
+
+# ---- what the launch plans decide once per call -----------------------------
+@gpu
+def test_zero_blocks_fall_back_to_the_default_grid(world, monkeypatch):
+    """A block count below 1 means the default grid (4096 dense, 8192 hash),
+    not a zero-block launch."""
+    run_route(world, monkeypatch, S6, kn(DNS, BK_DPART_BLOCKS=0), DENSE,
+              rng=(1, S6.n))
+    run_route(world, monkeypatch, S6, kn(DNS, BK_DPART_BLOCKS=0, BK_DPIPE=2),
+              DPIPE, rng=(1, S6.n))
+    run_route(world, monkeypatch, S1, kn(HASH, BK_PART_BLOCKS=0), PART)
+    run_route(world, monkeypatch, S1, kn(HASH, BK_PART_BLOCKS=0, BK_PIPE=2),
+              PIPE)
+
+
+@gpu
+@pytest.mark.parametrize("dp", [None, 2], ids=["single", "dpipe2"])
+@pytest.mark.parametrize("sh", [S6, S3_F2], ids=repr)
+def test_dense_absorb_takes_precedence_over_pack32(world, monkeypatch, sh, dp):
+    """With BK_DABS on, BK_DREC_PACK changes nothing: same integers as the
+    absorbing run alone."""
+    pipe = dict(BK_DPIPE=dp) if dp else {}
+    route = DPIPE if dp else DENSE
+    dabs = kn(DNS, BK_DABS=1, BK_DABS_MIN=0, **pipe)
+    ref = run_route(world, monkeypatch, sh, dabs, route)
+    got = run_route(world, monkeypatch, sh, kn(dabs, BK_DREC_PACK=1), route)
+    assert_same_ints(sh, got, ref)
+
+
+@gpu
+def test_dense_masked_scatter_ignores_pack32(world, monkeypatch):
+    """BK_NO_DEAGER switches off the eager scatter and PACK32 with it."""
+    masked = kn(DNS, BK_NO_DEAGER=1)
+    ref = run_route(world, monkeypatch, S6, masked, DENSE)
+    got = run_route(world, monkeypatch, S6, kn(masked, BK_DREC_PACK=1), DENSE)
+    assert_same_ints(S6, got, ref)
+
+
+@gpu
+def test_dense_absorb_on_but_no_chunk_absorbs(world, monkeypatch):
+    """BK_DABS_MIN=2 asks the hottest bucket for twice the chunk's survivors:
+    no chunk absorbs, and the non-absorbing chunks still run the unsplit
+    record layout (absorb on rules PACK32 out for the whole call)."""
+    ref = run_route(world, monkeypatch, S6, DNS, DENSE)
+    got = run_route(world, monkeypatch, S6,
+                    kn(DNS, BK_DABS=1, BK_DABS_MIN=2, BK_DREC_PACK=1), DENSE)
+    assert_same_ints(S6, got, ref)
+
+
+@gpu
+def test_dense_preference_below_one_still_dense(world, monkeypatch):
+    """BK_DENSE=-1 puts the sorted path first, BK_SORTED_RANGE=0 rules it
+    out: the dense route runs, not the hash partition."""
+    run_route(world, monkeypatch, S6, kn(BK_DENSE=-1, BK_SORTED_RANGE=0),
+              DENSE)
 
 
 # ---- sort-dedup routes (filter_agg_sorted directly) ---------------------------
