@@ -134,10 +134,15 @@ __device__ __forceinline__ Enc16 stage_enc16(const DevCol& c, int64_t rb,
     return o;
 }
 
-__device__ __forceinline__ Enc8 stage_enc8(const DevCol& c, int64_t rb,
-                                           uint64_t flip, uint64_t sub) {
+/* 8 consecutive rows from row rs + vo: rs is the wave's (scalar) base row, vo
+ * the lane's small offset, kept apart so the address is a scalar base plus a
+ * 32-bit lane offset instead of a 64-bit value per lane */
+__device__ __forceinline__ Enc8 stage_enc8(const DevCol& c, int64_t rs,
+                                           uint32_t vo, uint64_t flip,
+                                           uint64_t sub) {
     Enc8 o;
-    const char* p = (const char*)c.data + (rb << c.lshift);
+    const char* p = (const char*)c.data + (rs << c.lshift)
+                    + (size_t)(vo << c.lshift);
     if (c.lshift == 2) {
         uint64_t w[4];
         #pragma unroll
@@ -170,9 +175,10 @@ __device__ __forceinline__ Enc8 stage_enc8(const DevCol& c, int64_t rb,
 
 /* 8 consecutive rows of a width-8 column (f64 bits / wide int64): one full
  * 64 B line, 4 back-to-back 16 B loads */
-__device__ __forceinline__ W8 stage_w8(const void* data, int64_t rb) {
+__device__ __forceinline__ W8 stage_w8(const void* data, int64_t rs,
+                                       uint32_t vo) {
     W8 o;
-    const char* p = (const char*)data + ((uint64_t)rb << 3);
+    const char* p = (const char*)data + ((uint64_t)rs << 3) + (size_t)(vo << 3);
     #pragma unroll
     for (int i = 0; i < 4; i++)
         __builtin_memcpy(&o.v[2 * i], p + 16 * i, 16);
@@ -242,7 +248,7 @@ __device__ __forceinline__ uint32_t conj_mask16(const BkConjunct& cj,
 template <int BS, bool SIMPLE, bool VEC, int KV, int NCJ = 4>
 __global__ void __launch_bounds__(BS)
 k_dhisto(DevCols cols, BkQuerySpec q, DenseSpec ds, int64_t row_begin,
-         int64_t row_end, uint16_t* passbits, uint32_t* H,
+         int64_t row_end, uint16_t* passbits, uint32_t* H, uint32_t* totals,
          uint64_t* rows_passed) {
     constexpr int T = DPART_T;
     extern __shared__ __attribute__((aligned(16))) uint64_t laux_[];
@@ -319,8 +325,13 @@ k_dhisto(DevCols cols, BkQuerySpec q, DenseSpec ds, int64_t row_begin,
     if (threadIdx.x == 0)
         atomicAdd((unsigned long long*)rows_passed,
                   (unsigned long long)laux_[0]);
-    for (uint32_t b = threadIdx.x; b < ds.P; b += BS)
-        H[(size_t)blockIdx.x * ds.P + b] = lhist[b];
+    /* per-block counts for the scatter's reservation, bucket totals for the
+     * scan (as k_part_histo) */
+    for (uint32_t b = threadIdx.x; b < ds.P; b += BS) {
+        uint32_t n = lhist[b];
+        H[(size_t)blockIdx.x * ds.P + b] = n;
+        if (n) atomicAdd(&totals[b], n);
+    }
 }
 
 /* place one 32- or 64-bit field into the record register block */
@@ -388,12 +399,12 @@ template <int BS, bool SIMPLE>
 __global__ void __launch_bounds__(BS)
 k_dscatter(DevCols cols, BkQuerySpec q, DenseSpec ds, DRecLayout lay,
            int64_t row_begin, int64_t row_end, const uint16_t* passbits,
-           const uint32_t* H, uint64_t* rec) {
+           const uint32_t* H, uint32_t* base, uint64_t* rec) {
     constexpr int T = DPART_T;
     extern __shared__ __attribute__((aligned(16))) uint64_t lmem[];
     uint32_t* lcur = (uint32_t*)lmem;
     for (uint32_t b = threadIdx.x; b < ds.P; b += BS)
-        lcur[b] = H[(size_t)blockIdx.x * ds.P + b];
+        lcur[b] = part_reserve(H, base, ds.P, b);
     __syncthreads();
     int64_t gstride = (int64_t)gridDim.x * BS;
     int64_t lin = (int64_t)blockIdx.x * BS + threadIdx.x;
@@ -525,8 +536,8 @@ template <int BS, int NK, int NAR, int NF, bool ABS = false, bool PK = false>
 __global__ void __launch_bounds__(BS)
 k_dscatter_e(DevCols cols, BkQuerySpec q, DenseSpec ds, DRecLayout lay,
              DScatE prm, int64_t row_begin, int64_t row_end,
-             const uint16_t* passbits, const uint32_t* H, uint64_t* rec,
-             uint32_t* hdr, uint32_t hb, uint64_t* vslab, uint32_t* tslab) {
+             const uint16_t* passbits, const uint32_t* H, uint32_t* base,
+             uint64_t* rec, uint32_t* hdr, uint32_t hb, uint64_t* vslab, uint32_t* tslab) {
     constexpr int T = DPART_T;
     constexpr int NU32 = 1 + NAR;
     constexpr int WOFF = (NU32 + 1) / 2;          /* wide fields word base */
@@ -543,16 +554,39 @@ k_dscatter_e(DevCols cols, BkQuerySpec q, DenseSpec ds, DRecLayout lay,
         for (uint32_t i = threadIdx.x; i < win; i += BS) ltou[i] = 0;
     }
     for (uint32_t b = threadIdx.x; b < ds.P; b += BS)
-        lcur[b] = H[(size_t)blockIdx.x * ds.P + b];
+        lcur[b] = part_reserve(H, base, ds.P, b);
     __syncthreads();
     int64_t gstride = (int64_t)gridDim.x * BS;
-    int64_t lin = (int64_t)blockIdx.x * BS + threadIdx.x;
-    for (int64_t b0 = row_begin + lin * T; b0 < row_end; b0 += gstride * T) {
-        uint32_t pb = passbits[(b0 - row_begin) / T];
+    /* the loop walks the WAVE's base row (scalar: readfirstlane of a value
+     * every lane of a wave shares); a lane's rows are that base plus a small
+     * lane offset. A wave's 64 tiles are 1024 consecutive rows = 128
+     * half-tiles, and H counts per block, so the wave may deal them to its
+     * lanes freely. When the whole span is in range, lane l takes half-tile
+     * 64h + l in pass h, so neighbouring lanes stage neighbouring 8-row
+     * pieces: the two halves of a 128 B line of an 8-byte column load in the
+     * same instructions, not a j-loop apart (4-byte columns share a line over
+     * 4 lanes, 2-byte columns coalesce fully). passbits is little-endian u16
+     * per tile: byte k = half-tile k. A wave that crosses row_end keeps
+     * tile-per-lane, scalar tail tile included. */
+    const uint32_t lane = threadIdx.x & 63u;
+    const int64_t wlin = (int64_t)blockIdx.x * BS +
+        (__builtin_amdgcn_readfirstlane((int)threadIdx.x) & ~63);
+    for (int64_t wb = row_begin + wlin * T; wb < row_end; wb += gstride * T) {
+        const bool whole = wb + 64 * T <= row_end;
+        uint32_t pb;
+        if (whole) {
+            const uint8_t* pby =
+                (const uint8_t*)passbits + (wb - row_begin) / 8;
+            pb = (uint32_t)pby[lane] | ((uint32_t)pby[64 + lane] << 8);
+        } else {
+            if (wb + lane * T >= row_end) continue;
+            pb = passbits[(wb - row_begin) / T + lane];
+        }
         if (!pb) continue;
-        if (b0 + T > row_end) {                    /* tail tile: scalar,
+        if (!whole && wb + lane * T + T > row_end) {   /* tail tile: scalar,
                                                       same compile-time
                                                       field walk */
+            const int64_t b0 = wb + lane * T;
             while (pb) {
                 int j = __builtin_ctz(pb);
                 pb &= pb - 1;
@@ -634,14 +668,15 @@ k_dscatter_e(DevCols cols, BkQuerySpec q, DenseSpec ds, DRecLayout lay,
         for (int h = 0; h < 2; h++) {
             uint32_t sub8 = (pb >> (8 * h)) & 0xFFu;
             if (!sub8) continue;                   /* no loads, no work */
-            int64_t rb = b0 + 8 * h;
+            const uint32_t vo = whole ? 8 * (64 * h + lane)
+                                      : T * lane + 8 * h;
             const DevCol& c0 = cols.c[q.group_cols[0]];
             uint64_t flip0 = c0.type == BK_STRING ? 0 : (1ull << 63);
-            Enc8 dd = stage_enc8(c0, rb, flip0, ds.base0);
+            Enc8 dd = stage_enc8(c0, wb, vo, flip0, ds.base0);
             if (NK == 2) {
                 const DevCol& c1 = cols.c[q.group_cols[1]];
                 uint64_t flip1 = c1.type == BK_STRING ? 0 : (1ull << 63);
-                Enc8 d1 = stage_enc8(c1, rb, flip1, ds.base1);
+                Enc8 d1 = stage_enc8(c1, wb, vo, flip1, ds.base1);
                 #pragma unroll
                 for (int j = 0; j < 8; j++)
                     dd.d[j] = (dd.d[j] << ds.k1bits) | d1.d[j];
@@ -649,12 +684,12 @@ k_dscatter_e(DevCols cols, BkQuerySpec q, DenseSpec ds, DRecLayout lay,
             Enc8 nf[NAR > 0 ? NAR : 1];
             #pragma unroll
             for (int i = 0; i < NAR; i++)
-                nf[i] = stage_enc8(cols.c[prm.ncol[i]], rb, prm.nflip[i],
+                nf[i] = stage_enc8(cols.c[prm.ncol[i]], wb, vo, prm.nflip[i],
                                    prm.nsub[i]);
             W8 wf[NF > 0 ? NF : 1];
             #pragma unroll
             for (int i = 0; i < NF; i++)
-                wf[i] = stage_w8(cols.c[prm.wcol[i]].data, rb);
+                wf[i] = stage_w8(cols.c[prm.wcol[i]].data, wb, vo);
             #pragma unroll
             for (int j = 0; j < 8; j++) {
                 if (!((sub8 >> j) & 1u)) continue;
@@ -976,7 +1011,6 @@ struct DensePlan {
     const BkQuerySpec* qk;      /* SIMPLE: the padded copy (points into this
                                  * plan: plans are not copied) */
     int nblocks, threads;       /* histo + scatter grid and block shape */
-    uint32_t nch;               /* OFFS_CHUNK tiles of the per-block counts */
     DHistoFn histo_fn;
     DScatFn scat_fn;            /* masked scatter, when no eager plan holds */
     DScatEFn scat_e, scat_abs;  /* eager scatter, its absorbing twin, or null */
@@ -1237,7 +1271,6 @@ static bool dense_plan(DensePlan* pl, BkgTable* t, const BkQuerySpec* q) {
     pl->nblocks = 4096;
     if (const char* e = getenv("BK_DPART_BLOCKS")) pl->nblocks = atoi(e);
     if (pl->nblocks < 1) pl->nblocks = 4096;    /* no zero-block launch */
-    pl->nch = (uint32_t)((pl->nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK);
     pl->threads = 512;
     DevCols dc = table_cols(t);
 
@@ -1346,7 +1379,7 @@ static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
     ChunkSplit sp(row_begin, row_end, npipe);
     if (sp.piped() && !sp.streams) return -1;
     DevCols dc = table_cols(t);
-    const uint32_t P = ds.P, nch = pl.nch;
+    const uint32_t P = ds.P;
     const int nblocks = pl.nblocks, threads = pl.threads;
     const uint64_t span_alloc = (uint64_t)P << ds.shift;
 
@@ -1368,7 +1401,7 @@ static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
     uint64_t per_tiles = (uint64_t)((sp.per + DPART_T - 1) / DPART_T);
     for (int i = 0; i < sp.nslots(); i++) {
         CHK("dense", pool_alloc((void**)&sl[i].passbits, per_tiles * 2 + 16));
-        CHK("dense", sl[i].alloc_prefix(nblocks, P, nch));
+        CHK("dense", sl[i].alloc_prefix(nblocks, P));
     }
     const size_t gvals_bytes = (size_t)span_alloc * ds.nv * 8 + 8;
     CHK("dense", pool_alloc((void**)&gvals, gvals_bytes));
@@ -1392,10 +1425,10 @@ static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
         CHK("dense", hipMemsetAsync(s.totals, 0, (size_t)P * 4, st));
         hipLaunchKernelGGL(pl.histo_fn, dim3(nblocks), dim3(threads),
                            pl.histo_lds, st, dc, *pl.qk, ds, k.cb, k.ce,
-                           s.passbits, s.H, o->ctrs + 1);
+                           s.passbits, s.H, s.totals, o->ctrs + 1);
         ck.mark();
         uint64_t total = 0;
-        CHK("dense", prefix_pass(s, nblocks, P, nch, st, ck, &total,
+        CHK("dense", prefix_pass(s, P, st, ck, &total,
                                  h_tot.data(), h_base.data()));
         /* hottest bucket of THIS chunk (measured counts; first of equals) */
         const uint32_t hotb = (uint32_t)(
@@ -1417,20 +1450,20 @@ static int run_dense(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
                     CHK("dense", pool_alloc((void**)&s.tslab, slab * 4));
                 hipLaunchKernelGGL(pl.scat_abs, dim3(nblocks), dim3(threads),
                                    pl.abs_lds, st, dc, *pl.qk, ds, lay,
-                                   pl.eprm, k.cb, k.ce, s.passbits, s.H, s.rec,
-                                   nullptr, hotb << ds.shift, s.vslab, s.tslab);
+                                   pl.eprm, k.cb, k.ce, s.passbits, s.H,
+                                   s.base, s.rec, nullptr, hotb << ds.shift, s.vslab, s.tslab);
                 hipLaunchKernelGGL(k_dabs_reduce, dim3(256), dim3(256), 0, st,
                                    ds, hotb << ds.shift, (uint32_t)nblocks,
                                    s.vslab, s.tslab, gvals, gtouch);
             } else if (pl.scat_e)
                 hipLaunchKernelGGL(pl.scat_e, dim3(nblocks), dim3(threads),
                                    pl.scat_lds, st, dc, *pl.qk, ds, lay,
-                                   pl.eprm, k.cb, k.ce, s.passbits, s.H, s.rec,
-                                   hdrp, 0u, nullptr, nullptr);
+                                   pl.eprm, k.cb, k.ce, s.passbits, s.H,
+                                   s.base, s.rec, hdrp, 0u, nullptr, nullptr);
             else
                 hipLaunchKernelGGL(pl.scat_fn, dim3(nblocks), dim3(threads),
                                    pl.scat_lds, st, dc, *pl.qk, ds, lay, k.cb,
-                                   k.ce, s.passbits, s.H, s.rec);
+                                   k.ce, s.passbits, s.H, s.base, s.rec);
         }
         ck.mark();
         /* descriptors: per bucket, runs of <= CH records (balances skewed

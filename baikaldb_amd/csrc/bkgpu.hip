@@ -1364,7 +1364,7 @@ __device__ __forceinline__ void histo_row(
 template <int BS, bool HOT, bool SIMPLE = false>
 __global__ void __launch_bounds__(BS)
 k_part_histo(DevCols cols, BkQuerySpec q, int64_t row_begin, int64_t row_end,
-             uint32_t P, uint16_t* bucketid, uint32_t* H,
+             uint32_t P, uint16_t* bucketid, uint32_t* H, uint32_t* totals,
              uint64_t* gtable, uint64_t gmask, uint64_t fill_cap, uint64_t* fill,
              uint64_t* rows_passed, uint32_t* err, uint32_t lds_slots,
              uint32_t lcap, uint32_t hot_probe, uint32_t hot_min) {
@@ -1397,8 +1397,13 @@ k_part_histo(DevCols cols, BkQuerySpec q, int64_t row_begin, int64_t row_end,
     __syncthreads();
     if (threadIdx.x == 0)
         atomicAdd((unsigned long long*)rows_passed, (unsigned long long)laux[1]);
-    for (uint32_t b = threadIdx.x; b < P; b += blockDim.x)
-        H[(size_t)blockIdx.x * P + b] = lhist[b];
+    /* per-block counts for the scatter's reservation, bucket totals for the
+     * scan (no-return atomics, coalesced over b; totals zeroed by the host) */
+    for (uint32_t b = threadIdx.x; b < P; b += blockDim.x) {
+        uint32_t n = lhist[b];
+        H[(size_t)blockIdx.x * P + b] = n;
+        if (n) atomicAdd(&totals[b], n);
+    }
     /* flush this block's hot groups into the global table */
     if (HOT) {
         __syncthreads();
@@ -1411,24 +1416,6 @@ k_part_histo(DevCols cols, BkQuerySpec q, int64_t row_begin, int64_t row_end,
             agg_merge_slot<false>(g, s + SLOT_HDR, q);
         }
     }
-}
-
-/* bucket totals over all blocks, tiled (b, chunk-of-blocks) for parallelism;
- * per-tile partials S[chunk][b] are reused by k_part_offsets. */
-#define OFFS_CHUNK 128u
-__global__ void k_part_totals(const uint32_t* H, uint32_t nblocks, uint32_t P,
-                              uint32_t* S, uint32_t* totals) {
-    uint32_t nchunks = (nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK;
-    uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= P * nchunks) return;
-    uint32_t b = idx % P, chunk = idx / P;
-    uint32_t b1 = (chunk + 1) * OFFS_CHUNK;
-    if (b1 > nblocks) b1 = nblocks;
-    uint32_t s = 0;
-    for (uint32_t blk = chunk * OFFS_CHUNK; blk < b1; blk++)
-        s += H[(size_t)blk * P + b];
-    S[(size_t)chunk * P + b] = s;
-    atomicAdd(&totals[b], s);
 }
 
 /* exclusive scan of totals -> base; grand total -> total_out. One workgroup,
@@ -1460,22 +1447,16 @@ k_part_scan(const uint32_t* totals, uint32_t P, uint32_t* base,
     if (threadIdx.x == T - 1 && total_out) *total_out = part[T - 1];
 }
 
-/* turn H[blk][b] counts into absolute start offsets, tiled like totals */
-__global__ void k_part_offsets(uint32_t* H, uint32_t nblocks, uint32_t P,
-                               const uint32_t* base, const uint32_t* S) {
-    uint32_t nchunks = (nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK;
-    uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= P * nchunks) return;
-    uint32_t b = idx % P, chunk = idx / P;
-    uint32_t run = base[b];
-    for (uint32_t c = 0; c < chunk; c++) run += S[(size_t)c * P + b];
-    uint32_t b1 = (chunk + 1) * OFFS_CHUNK;
-    if (b1 > nblocks) b1 = nblocks;
-    for (uint32_t blk = chunk * OFFS_CHUNK; blk < b1; blk++) {
-        uint32_t t = H[(size_t)blk * P + b];
-        H[(size_t)blk * P + b] = run;
-        run += t;
-    }
+/* a scatter block's start inside bucket b: it reserves the H[block][b] records
+ * its histogram twin counted, by bumping the bucket's cursor. The cursors
+ * start as k_part_scan's bases (the host took its copy of those before the
+ * scatter was queued), so a bucket's blocks fill [base, base + total) in
+ * arrival order — every reader of the records is order-free. */
+__device__ __forceinline__ uint32_t part_reserve(const uint32_t* H,
+                                                 uint32_t* base, uint32_t P,
+                                                 uint32_t b) {
+    uint32_t cnt = H[(size_t)blockIdx.x * P + b];
+    return cnt ? atomicAdd(&base[b], cnt) : 0;
 }
 
 /* widest-stores record flush (nt measured worse: partial-line nt stores are
@@ -1617,7 +1598,8 @@ template <int BS, bool SIMPLE = false>
 __global__ void __launch_bounds__(BS)
 k_part_scatter(DevCols cols, BkQuerySpec q, RecLayout lay, int64_t row_begin,
                int64_t row_end, uint32_t P, const uint16_t* bucketid,
-               const uint32_t* H, uint64_t* rec, uint64_t total, int paired) {
+               const uint32_t* H, uint32_t* base, uint64_t* rec,
+               uint64_t total, int paired) {
     /* LDS carve: [ stash: P*nwords u64 (pairing only) ][ lcur: P u32 ]
      *            [ bstate: P u32 ] */
     extern __shared__ __attribute__((aligned(16))) uint64_t lmem[];
@@ -1625,7 +1607,7 @@ k_part_scatter(DevCols cols, BkQuerySpec q, RecLayout lay, int64_t row_begin,
     uint32_t* lcur = (uint32_t*)(lmem + (paired ? (size_t)P * lay.nwords : 0));
     uint32_t* bstate = lcur + P;
     for (uint32_t b = threadIdx.x; b < P; b += blockDim.x) {
-        lcur[b] = H[(size_t)blockIdx.x * P + b];
+        lcur[b] = part_reserve(H, base, P, b);
         if (paired) bstate[b] = 0;
     }
     __syncthreads();
@@ -3135,19 +3117,18 @@ struct ChunkSplit {
  * arrays (sized once per call), the chunk's records (sized per chunk). A
  * route's slot derives from this and adds its own. */
 struct ChunkBufs {
-    uint32_t *H = nullptr, *totals = nullptr, *base = nullptr, *S = nullptr;
+    uint32_t *H = nullptr, *totals = nullptr, *base = nullptr;
     uint64_t *total_dev = nullptr, *rec = nullptr;
-    hipError_t alloc_prefix(int nblocks, uint32_t P, uint32_t nch) {
+    hipError_t alloc_prefix(int nblocks, uint32_t P) {
         hipError_t e = pool_alloc((void**)&H, (size_t)nblocks * P * 4);
         if (!e) e = pool_alloc((void**)&totals, (size_t)P * 4);
         if (!e) e = pool_alloc((void**)&base, (size_t)P * 4);
-        if (!e) e = pool_alloc((void**)&S, (size_t)nch * P * 4);
         if (!e) e = pool_alloc((void**)&total_dev, 8);
         return e;
     }
     void recycle() { pool_free(rec); rec = nullptr; }   /* per-chunk part */
     void release() {
-        pool_free(H); pool_free(totals); pool_free(base); pool_free(S);
+        pool_free(H); pool_free(totals); pool_free(base);
         pool_free(total_dev); pool_free(rec);
     }
 };
@@ -3193,17 +3174,18 @@ struct ChunkClock {
     }
 };
 
-/* between a chunk's histogram (H[block][bucket] counts) and its scatter:
- * bucket totals, their exclusive scan, per-block start offsets. The records
+/* between a chunk's histogram and its scatter: the exclusive scan of the
+ * bucket totals (the histogram blocks added them up themselves). The records
  * are sized from the chunk total, so the host waits for this chunk's stream
- * here (the other keeps running); h_tot / h_base ride along in that wait. */
-static hipError_t prefix_pass(const ChunkBufs& b, int nblocks, uint32_t P,
-                              uint32_t nch, hipStream_t st, ChunkClock& ck,
-                              uint64_t* total, uint32_t* h_tot = nullptr,
+ * here (the other keeps running); h_tot / h_base ride along in that wait —
+ * taken before the scatter, whose blocks then use `base` as the buckets'
+ * cursors (part_reserve). The single pass keeps its seven / six breakdown
+ * names: the intervals once spent in the totals and offsets kernels
+ * ("dtotals"/"doffs", "totals"/"offsets") now time an empty stretch. */
+static hipError_t prefix_pass(const ChunkBufs& b, uint32_t P, hipStream_t st,
+                              ChunkClock& ck, uint64_t* total,
+                              uint32_t* h_tot = nullptr,
                               uint32_t* h_base = nullptr) {
-    const dim3 tiles((P * nch + 255) / 256);
-    hipLaunchKernelGGL(k_part_totals, tiles, dim3(256), 0, st, b.H, nblocks,
-                       P, b.S, b.totals);
     ck.mark();
     hipLaunchKernelGGL(k_part_scan, dim3(1), dim3(1024), 0, st, b.totals, P,
                        b.base, b.total_dev);
@@ -3215,8 +3197,6 @@ static hipError_t prefix_pass(const ChunkBufs& b, int nblocks, uint32_t P,
     if (!e && h_base) e = hipMemcpyAsync(h_base, b.base, (size_t)P * 4, D2H, st);
     if (!e) e = hipStreamSynchronize(st);
     if (e) return e;
-    hipLaunchKernelGGL(k_part_offsets, tiles, dim3(256), 0, st, b.H, nblocks,
-                       P, b.base, b.S);
     ck.mark();
     return hipSuccess;
 }
@@ -3229,7 +3209,6 @@ static hipError_t prefix_pass(const ChunkBufs& b, int nblocks, uint32_t P,
 struct PartPlan {
     uint32_t P;                 /* hash buckets (a power of two) */
     int nblocks, threads;       /* histo + scatter grid and block shape */
-    uint32_t nch;               /* OFFS_CHUNK tiles of the per-block counts */
     RecLayout lay;
     bool simple;
     BkQuerySpec qpad;
@@ -3267,7 +3246,6 @@ static void part_plan(PartPlan* pl, BkgTable* t, const BkQuerySpec* q,
     pl->nblocks = 8192;
     if (const char* e = getenv("BK_PART_BLOCKS")) pl->nblocks = atoi(e);
     if (pl->nblocks < 1) pl->nblocks = 8192;    /* no zero-block launch */
-    pl->nch = (uint32_t)((pl->nblocks + OFFS_CHUNK - 1) / OFFS_CHUNK);
     /* histo+scatter MUST share grid AND block shape (H rows are per-block).
      * 512 threads measured best (histo 5.7->3.4 ms, scatter 9.9->8.3 ms at
      * 3e8 rows): 8 waves/block hides more gather latency; 1024 regresses
@@ -3372,7 +3350,7 @@ static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
         set_err("row chunk too large for one pass");
         return -1;
     }
-    const uint32_t P = pl.P, nch = pl.nch;
+    const uint32_t P = pl.P;
     const int nblocks = pl.nblocks, threads = pl.threads;
 
     struct Slot : ChunkBufs { uint16_t* bucketid = nullptr; } sl[2];
@@ -3381,7 +3359,7 @@ static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
     };
     for (int i = 0; i < sp.nslots(); i++) {
         CHK("part", pool_alloc((void**)&sl[i].bucketid, (size_t)sp.per * 2));
-        CHK("part", sl[i].alloc_prefix(nblocks, P, nch));
+        CHK("part", sl[i].alloc_prefix(nblocks, P));
     }
     DevCols dc = table_cols(t);
 
@@ -3399,12 +3377,12 @@ static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
         ck.mark();
         hipLaunchKernelGGL(pl.histo_fn, dim3(nblocks), dim3(threads),
                            pl.histo_lds, st, dc, *pl.qk, k.cb, k.ce, P,
-                           s.bucketid, s.H, o->table, o->nslots - 1,
+                           s.bucketid, s.H, s.totals, o->table, o->nslots - 1,
                            (o->nslots * 7) / 8, o->ctrs, o->ctrs + 1, o->err,
                            pl.hot_slots, pl.hot_cap, pl.hot_probe, pl.hot_min);
         ck.mark();
         uint64_t total = 0;
-        CHK("part", prefix_pass(s, nblocks, P, nch, st, ck, &total));
+        CHK("part", prefix_pass(s, P, st, ck, &total));
         if (!piped && debug_timing()) {
             uint64_t passed = 0;
             (void)hipMemcpy(&passed, o->ctrs + 1, 8, hipMemcpyDeviceToHost);
@@ -3422,7 +3400,7 @@ static int run_partitioned(BkgAggOut* o, BkgTable* t, const BkQuerySpec* q,
             size_t sc_lds = paired ? pair_lds : (size_t)P * 8;
             hipLaunchKernelGGL(pl.scat_fn, dim3(nblocks), dim3(threads), sc_lds,
                                st, dc, *pl.qk, pl.lay, k.cb, k.ce, P, s.bucketid,
-                               s.H, s.rec, total, paired);
+                               s.H, s.base, s.rec, total, paired);
         }
         ck.mark();
         if (total > 0) {
