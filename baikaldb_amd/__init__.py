@@ -7,4 +7,4 @@
 # engine refuses to run without the native extension (the CPU oracle under
 # oracle/ is test infrastructure only).
 from .engine import GpuEngine, GpuTable, NativeEngineMissing  # noqa: F401
-from .plan import QueryPlan  # noqa: F401
+from .plan import QueryPlan, JoinPlan  # noqa: F401

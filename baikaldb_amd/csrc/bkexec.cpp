@@ -236,6 +236,10 @@ static ScanNode* find_scan(ExecNode* n);
  *    AggNode's materialized table (canonical group order) under the
  *    conjuncts of the HAVING_FILTER_NODEs passed on the way; columns are
  *    then slot indices into [group keys...][agg outputs...];
+ *  - a JOIN_NODE makes it the joined table (JoinNode::result_table) under
+ *    the WHERE filter passed on the way; columns are then positions in the
+ *    join's output list (from_agg is set: the counters stay as the JoinNode
+ *    set them, and a 0-row source skips the kernels);
  *  - otherwise it is the scan's table under the WHERE filter. */
 struct Source {
     BkgTable* table = nullptr;
@@ -701,6 +705,151 @@ private:
     BkgTable* _result = nullptr;   /* materialized table (result_table) */
 };
 
+/* ---- JoinNode (join_node.cpp / joiner.cpp hash join). Two children, each
+ * [WHERE ->] SCAN: children[0] is the outer side, children[1] the inner
+ * side; a child's WHERE conjuncts restrict that side before the join (the
+ * reference pushes such filters below the join's children). run() compiles
+ * the subtree into one bkgpu_join call; the result is a device-resident
+ * table whose columns are the node's output list, in the order bkgpu_join
+ * documents. A node above consumes it through result_table() (source_of);
+ * as the root, get_next() streams its rows in result order. ---- */
+class JoinNode : public ExecNode {
+public:
+    int init(const BkPlanNodeDesc& node) override {
+        ExecNode::init(node);
+        _desc = node;
+        if (node.num_children != 2) return -1;
+        if (_desc.n_join_out < 1 || _desc.n_join_out > BK_MAX_COLS) return -1;
+        return 0;
+    }
+    ~JoinNode() override { if (_result) bkgpu_table_free(_result); }
+    int open(RuntimeState* state) override {
+        if (!_result && run(state) < 0) return -1;
+        _nrows = bkgpu_table_nrows(_result);
+        _pos = 0;
+        _iter = 0;
+        _chunk_n = 0;
+        return 0;
+    }
+    BkgTable* result_table(RuntimeState* state) {
+        if (!_result && run(state) < 0) return nullptr;
+        return _result;
+    }
+    int n_slots() const { return _desc.n_join_out; }
+    int get_next(RuntimeState* state, RowBatch* batch, bool* eos) override {
+        const int nc = n_slots();
+        while (true) {
+            if (state->is_cancelled()) { *eos = true; return 0; }
+            if (reached_limit()) { *eos = true; return 0; }
+            if (_iter >= _chunk_n) {
+                if (_pos >= _nrows) { *eos = true; return 0; }
+                if (fetch_chunk(state) < 0) return -1;
+            }
+            if (batch->is_full()) return 0;
+            auto row = std::make_unique<MemRow>(nc);
+            for (int c = 0; c < nc; c++) {
+                ExprValue v;
+                v.type = _col_types[c];
+                v.is_null_ = _cols_n[c][_iter] != 0;
+                if (!v.is_null_) {
+                    if (v.type == BK_DOUBLE) v.d = _cols_d[c][_iter];
+                    else v.i = _cols_i[c][_iter];
+                }
+                row->set_value(c, v);
+            }
+            batch->move_row(std::move(row));
+            _num_rows_returned++;
+            _iter++;
+        }
+    }
+    void close(RuntimeState* state) override {
+        ExecNode::close(state);
+        if (_result) { bkgpu_table_free(_result); _result = nullptr; }
+        _rowids.clear();
+        _cols_i.clear(); _cols_d.clear(); _cols_n.clear();
+        _nrows = _pos = _iter = _chunk_n = 0;
+    }
+private:
+    /* one side: [WHERE ->] SCAN */
+    static int side_of(ExecNode* n, RuntimeState* state, BkgTable** t,
+                       BkQuerySpec* q) {
+        if (n->node_type() == BK_TABLE_FILTER_NODE ||
+            n->node_type() == BK_WHERE_FILTER_NODE) {
+            FilterNode* f = static_cast<FilterNode*>(n);
+            q->n_conjuncts = f->n_conjuncts();
+            memcpy(q->conjuncts, f->conjuncts(), sizeof(q->conjuncts));
+            n = n->children().empty() ? nullptr : n->children()[0];
+        }
+        if (!n || n->node_type() != BK_SCAN_NODE) {
+            state->error_msg = "JoinNode: each child must be [WHERE ->] SCAN";
+            return -1;
+        }
+        *t = static_cast<ScanNode*>(n)->table();
+        return 0;
+    }
+    int run(RuntimeState* state) {
+        if (_children.size() != 2) {
+            state->error_msg = "JoinNode needs two children";
+            return -1;
+        }
+        BkgTable *outer = nullptr, *inner = nullptr;
+        BkQuerySpec qo{}, qi{};
+        if (side_of(_children[0], state, &outer, &qo) < 0 ||
+            side_of(_children[1], state, &inner, &qi) < 0)
+            return -1;
+        BkJoinSpec s{};
+        s.join_type = _desc.join_type;
+        s.n_keys = _desc.n_join_keys;
+        for (int k = 0; k < BK_MAX_JOIN_KEYS; k++) {
+            s.outer_key[k] = _desc.join_outer_key[k];
+            s.inner_key[k] = _desc.join_inner_key[k];
+        }
+        s.n_out = _desc.n_join_out;
+        for (int c = 0; c < BK_MAX_COLS; c++) {
+            s.out_side[c] = _desc.join_out_side[c];
+            s.out_col[c] = _desc.join_out_col[c];
+        }
+        _result = bkgpu_join(outer, &qo, inner, &qi, &s);
+        if (!_result) { state->error_msg = bkgpu_last_error(); return -1; }
+        /* num_scan_rows: both children's scanned rows */
+        const int64_t no = bkgpu_table_nrows(outer);
+        state->inc_num_scan_rows(no + bkgpu_table_nrows(inner));
+        int64_t st[8];
+        if (bkgpu_join_stats(st) == 0) state->inc_num_filter_rows(no - st[0]);
+        _col_types.resize(n_slots());
+        for (int c = 0; c < n_slots(); c++)
+            _col_types[c] = bkgpu_table_col_type(_result, c);
+        return 0;
+    }
+    int fetch_chunk(RuntimeState* state) {
+        const int nc = n_slots();
+        const int64_t n = std::min(_nrows - _pos, fetch_chunk_rows());
+        _rowids.resize(n);
+        for (int64_t i = 0; i < n; i++) _rowids[i] = _pos + i;
+        _cols_i.assign(nc, {}); _cols_d.assign(nc, {}); _cols_n.assign(nc, {});
+        for (int c = 0; c < nc; c++) {
+            _cols_i[c].resize(n); _cols_d[c].resize(n); _cols_n[c].resize(n);
+            if (bkgpu_gather(_result, c, _rowids.data(), n, _cols_i[c].data(),
+                             _cols_d[c].data(), _cols_n[c].data()) != 0) {
+                state->error_msg = bkgpu_last_error();
+                return -1;
+            }
+        }
+        _pos += n;
+        _chunk_n = n;
+        _iter = 0;
+        return 0;
+    }
+    BkPlanNodeDesc _desc{};
+    BkgTable* _result = nullptr;
+    std::vector<int32_t> _col_types;
+    std::vector<int64_t> _rowids;
+    std::vector<std::vector<int64_t>> _cols_i;
+    std::vector<std::vector<double>> _cols_d;
+    std::vector<std::vector<uint8_t>> _cols_n;
+    int64_t _nrows = 0, _pos = 0, _iter = 0, _chunk_n = 0;
+};
+
 static bool is_agg_node(const ExecNode* n) {
     return n->node_type() == BK_AGG_NODE || n->node_type() == BK_MERGE_AGG_NODE;
 }
@@ -728,6 +877,24 @@ static int source_of(ExecNode* node, RuntimeState* state, Source* src) {
             src->from_agg = true;
             src->q.n_conjuncts = n_having;
             memcpy(src->q.conjuncts, having, sizeof(BkConjunct) * n_having);
+            return 0;
+        } else if (ty == BK_JOIN_NODE) {
+            /* the joined table; columns above are output-list positions. A
+             * WHERE between the node and the join filters joined rows (how a
+             * non-equi ON condition is applied). Counters stay as the
+             * JoinNode set them, as over an aggregate. */
+            if (n_having) {
+                state->error_msg = "HAVING_FILTER_NODE without an aggregate below";
+                return -1;
+            }
+            src->table = static_cast<JoinNode*>(n)->result_table(state);
+            if (!src->table) return -1;
+            src->from_agg = true;
+            if (where) {
+                src->q.n_conjuncts = where->n_conjuncts();
+                memcpy(src->q.conjuncts, where->conjuncts(),
+                       sizeof(src->q.conjuncts));
+            }
             return 0;
         } else if (ty == BK_SCAN_NODE) {
             if (n_having) {
@@ -1067,6 +1234,7 @@ ExecNode* ExecNode::create_exec_node(const BkPlanNodeDesc& node) {
          * stay above the aggregate (filter_node.cpp:545-550) */
         case BK_HAVING_FILTER_NODE: return new FilterNode();
         case BK_LIMIT_NODE:        return new LimitNode();
+        case BK_JOIN_NODE:         return new JoinNode();
         default:                   return nullptr;
     }
 }
@@ -1120,6 +1288,8 @@ static int tree_n_slots(const BkExecTree* t) {
         return static_cast<SortNode*>(n)->n_slots();
     if (n->node_type() == BK_WINDOW_NODE)
         return static_cast<WindowNode*>(n)->n_slots();
+    if (n->node_type() == BK_JOIN_NODE)
+        return static_cast<JoinNode*>(n)->n_slots();
     if (n->node_type() == BK_TABLE_FILTER_NODE ||
         n->node_type() == BK_WHERE_FILTER_NODE ||
         n->node_type() == BK_HAVING_FILTER_NODE)   /* slots of the AGG below */

@@ -4137,3 +4137,4 @@ extern "C" int bkgpu_gather(BkgTable* t, int col, const int64_t* rowids_host,
 #include "bkwin.inc"
 #include "bkdedup.inc"
 #include "bkpost.inc"
+#include "bkjoin.inc"

@@ -8,7 +8,7 @@ import os
 import numpy as np
 
 from .plan import (BkQuerySpec, BkOrderSpec, BkWindowFn, QueryPlan,
-                   BK_MAX_GROUP, _WINFNS)
+                   BK_MAX_GROUP, _WINFNS, BkJoinSpec, JoinPlan)
 from .plan import TYPE_INT64, TYPE_DOUBLE, TYPE_STRING
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -192,6 +192,14 @@ def _load():
     lib.bkgpu_upload_bytes.restype = C.c_void_p
     lib.bkgpu_upload_bytes.argtypes = [C.c_void_p, C.c_int64]
     lib.bkgpu_free_ptr.argtypes = [C.c_void_p]
+    lib.bkgpu_join.restype = C.c_void_p
+    lib.bkgpu_join.argtypes = [C.c_void_p, C.POINTER(BkQuerySpec), C.c_void_p,
+                               C.POINTER(BkQuerySpec), C.POINTER(BkJoinSpec)]
+    lib.bkgpu_join_stats.restype = C.c_int
+    lib.bkgpu_join_stats.argtypes = [C.POINTER(C.c_int64)]
+    lib.bkgpu_join_stage_ms.restype = C.c_int
+    lib.bkgpu_join_stage_ms.argtypes = [C.POINTER(C.c_double)]
+    lib.bkgpu_join_tile_rows.restype = C.c_int64
     return lib
 
 
@@ -561,6 +569,59 @@ class GpuEngine:
 
     def topk_kernel_ms(self):
         return self.lib.bkgpu_topk_kernel_ms()
+
+    def _table_of(self, h, what):
+        """Wrap a BkgTable* an engine call returned (NULL raises)."""
+        if not h:
+            raise RuntimeError(f"{what}: {self.lib.bkgpu_last_error().decode()}")
+        lib = self.lib
+        ncols = lib.bkgpu_table_ncols(h)
+        types = [lib.bkgpu_table_col_type(h, c) for c in range(ncols)]
+        t = GpuTable(self, h, types, lib.bkgpu_table_nrows(h))
+        t.col_nullable = [bool(lib.bkgpu_table_col_nullable(h, c))
+                          for c in range(ncols)]
+        return t
+
+    def join(self, outer, inner, on, how="inner", out=None, outer_plan=None,
+             inner_plan=None):
+        """FROM outer JOIN inner ON outer.ocol = inner.icol [AND ...]
+        (bkgpu_join): on = [(ocol, icol), ...]; how = inner / left / right /
+        semi / anti; out = [(side, col), ...] with side 0 outer / 1 inner
+        (None: all outer columns, then all inner columns; outer only for
+        semi / anti). outer_plan / inner_plan: QueryPlans whose conjuncts
+        restrict a side before the join. Rows come out in ascending outer
+        row id, matches of one outer row in ascending inner row id. Returns
+        a GpuTable every other engine call accepts; the caller frees it."""
+        jp = JoinPlan(outer.col_types, inner.col_types, on, how, out)
+        if jp.swapped:      # right join: run as a left join, sides swapped
+            outer, inner = inner, outer
+            outer_plan, inner_plan = inner_plan, outer_plan
+        spec = jp.to_spec()
+        qo = outer_plan.to_spec() if outer_plan is not None else None
+        qi = inner_plan.to_spec() if inner_plan is not None else None
+        h = self.lib.bkgpu_join(outer.handle,
+                                C.byref(qo) if qo is not None else None,
+                                inner.handle,
+                                C.byref(qi) if qi is not None else None,
+                                C.byref(spec))
+        return self._table_of(h, "join")
+
+    def join_stats(self):
+        """The calling thread's last join (bkgpu_join_stats): row and key
+        counts, the route taken ("global" / "lds") and device time."""
+        v = (C.c_int64 * 8)()
+        ms = (C.c_double * 4)()
+        self._check(self.lib.bkgpu_join_stats(v), "join_stats")
+        self._check(self.lib.bkgpu_join_stage_ms(ms), "join_stats")
+        return {"outer_passed": v[0], "inner_passed": v[1],
+                "unique_keys": v[2], "slots": v[3], "rows": v[4],
+                "route": "lds" if v[5] else "global",
+                "kernel_ms": v[6] / 1000.0, "table_bytes": v[7],
+                "stage_ms": dict(zip(("build", "count", "emit", "gather"),
+                                     list(ms)))}
+
+    def join_tile_rows(self):
+        return int(self.lib.bkgpu_join_tile_rows())
 
     def window(self, table, fns, part_col=-1, order=(), plan: QueryPlan = None,
                frame=None, row_begin=0, row_end=None):

@@ -17,6 +17,7 @@ BK_MAX_COLS = 16
 SCAN, SORT, AGG, MERGE_AGG, TABLE_FILTER, LIMIT, WHERE_FILTER = 1, 2, 4, 5, 6, 11, 12
 WINDOW = 42
 HAVING_FILTER = 13   # plan.proto:24; built as a FilterNode above the aggregate
+JOIN = 7             # plan.proto:18
 
 
 class BkPlanNodeDesc(C.Structure):
@@ -43,7 +44,14 @@ class BkPlanNodeDesc(C.Structure):
                 ("winfns", BkWindowFn * 8),
                 ("frame_mode", C.c_int32),
                 ("_pad_w", C.c_int32),
-                ("frame_pre", C.c_int64), ("frame_fol", C.c_int64)]
+                ("frame_pre", C.c_int64), ("frame_fol", C.c_int64),
+                # JOIN_NODE payload, appended (bk_exec.h)
+                ("join_type", C.c_int32), ("n_join_keys", C.c_int32),
+                ("join_outer_key", C.c_int32 * 2),
+                ("join_inner_key", C.c_int32 * 2),
+                ("n_join_out", C.c_int32), ("_pad_j", C.c_int32),
+                ("join_out_side", C.c_int32 * BK_MAX_COLS),
+                ("join_out_col", C.c_int32 * BK_MAX_COLS)]
 
 
 def _bind(lib):
@@ -163,6 +171,26 @@ def agg_node(group, aggs, expected_groups=1 << 16, merge=False, num_children=1,
     return d
 
 
+def join_node(outer_types, inner_types, on, how="inner", out=None, limit=-1):
+    """JOIN_NODE with two children, each [WHERE ->] SCAN, outer side first
+    (plan.JoinPlan validates and fills the payload). For how="right" the
+    plan swaps the sides: the caller lists the children in the swapped order
+    (JoinPlan.swapped)."""
+    from .plan import JoinPlan
+    jp = JoinPlan(outer_types, inner_types, on, how, out)
+    d = BkPlanNodeDesc()
+    d.node_type, d.num_children = JOIN, 2
+    d.limit = limit
+    d.join_type = jp.join_type
+    d.n_join_keys = len(jp.on)
+    for i, (oc, ic) in enumerate(jp.on):
+        d.join_outer_key[i], d.join_inner_key[i] = oc, ic
+    d.n_join_out = len(jp.out)
+    for i, (side, col) in enumerate(jp.out):
+        d.join_out_side[i], d.join_out_col[i] = side, col
+    return d
+
+
 def sort_node(order, out_cols, limit, num_children=1):
     d = BkPlanNodeDesc()
     d.node_type, d.num_children = SORT, num_children
@@ -231,6 +259,10 @@ class ExecTree:
     @property
     def num_scan_rows(self):
         return self.lib.bkexec_num_scan_rows(self.handle)
+
+    @property
+    def num_rows_returned(self):
+        return self.lib.bkexec_num_rows_returned(self.handle)
 
     @property
     def num_filter_rows(self):

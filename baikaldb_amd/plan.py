@@ -456,3 +456,100 @@ class QueryPlan:
                 src_idx[i] = next_plain
                 next_plain += 1
         return l1, q2, src_idx
+
+
+# ---- equi-join (include/bkgpu.h BkJoinSpec; proto/plan.proto JoinType) ----
+NULL_JOIN, LEFT_JOIN, RIGHT_JOIN, INNER_JOIN = 0, 1, 2, 3
+SEMI_JOIN, ANTI_SEMI_JOIN, FULL_JOIN = 4, 5, 6
+BK_MAX_COLS, BK_MAX_JOIN_KEYS = 16, 2
+_JOINS = {"left": LEFT_JOIN, "right": RIGHT_JOIN, "inner": INNER_JOIN,
+          "semi": SEMI_JOIN, "anti": ANTI_SEMI_JOIN, "full": FULL_JOIN}
+
+
+class BkJoinSpec(C.Structure):
+    _fields_ = [("join_type", C.c_int32), ("n_keys", C.c_int32),
+                ("outer_key", C.c_int32 * BK_MAX_JOIN_KEYS),
+                ("inner_key", C.c_int32 * BK_MAX_JOIN_KEYS),
+                ("n_out", C.c_int32),
+                ("out_side", C.c_int32 * BK_MAX_COLS),
+                ("out_col", C.c_int32 * BK_MAX_COLS)]
+
+
+class JoinPlan:
+    """FROM outer JOIN inner ON outer.ocol = inner.icol [AND ...].
+
+    on:  [(outer_col, inner_col), ...], 1 or 2 pairs, both INT64 or both
+         DATETIME.
+    how: "inner" | "left" | "right" | "semi" | "anti".
+    out: [(side, col), ...] with side 0 = outer / "outer", 1 = inner /
+         "inner"; None = every outer column, then every inner column (outer
+         only for semi / anti).
+
+    A right join is not a kernel mode: like Joiner (joiner.cpp:134-139) the
+    plan swaps the sides and runs a left join. `swapped` tells the caller to
+    pass the tables (and their side filters) in the other order; the `out`
+    entries are mapped so the result's columns stay as requested."""
+
+    def __init__(self, outer_types, inner_types, on, how="inner", out=None):
+        if how not in _JOINS:
+            raise ValueError(f"unknown join type {how!r}")
+        if how == "full":
+            raise ValueError("FULL_JOIN is not supported")
+        outer_types, inner_types = list(outer_types), list(inner_types)
+        on = [tuple(p) for p in on]
+        if not 1 <= len(on) <= BK_MAX_JOIN_KEYS:
+            raise ValueError("a join needs 1 or 2 equality key pairs")
+        for oc, ic in on:
+            if not (0 <= oc < len(outer_types) and 0 <= ic < len(inner_types)):
+                raise ValueError(f"key column out of range: {(oc, ic)}")
+            ot, it = outer_types[oc], inner_types[ic]
+            if TYPE_DOUBLE in (ot, it):
+                raise ValueError("DOUBLE join keys are not supported")
+            if TYPE_STRING in (ot, it):
+                raise ValueError("STRING join keys are not supported (dict "
+                                 "codes of two tables are unrelated)")
+            if ot != it or ot not in (TYPE_INT64, TYPE_DATETIME):
+                raise ValueError("a key pair must be INT64/INT64 or "
+                                 "DATETIME/DATETIME")
+        semi = how in ("semi", "anti")
+        if out is None:
+            out = [(0, c) for c in range(len(outer_types))]
+            if not semi:
+                out += [(1, c) for c in range(len(inner_types))]
+        sides = {0: 0, 1: 1, "outer": 0, "inner": 1}
+        norm = []
+        for side, col in out:
+            if side not in sides:
+                raise ValueError(f"bad output side {side!r}")
+            side = sides[side]
+            if side == 1 and semi:
+                raise ValueError("semi / anti joins output outer columns only")
+            if not 0 <= col < len(inner_types if side else outer_types):
+                raise ValueError(f"output column out of range: {(side, col)}")
+            norm.append((side, col))
+        if not 1 <= len(norm) <= BK_MAX_COLS:
+            raise ValueError(f"a join outputs 1..{BK_MAX_COLS} columns")
+        self.how = how
+        self.swapped = how == "right"
+        if self.swapped:
+            # the caller's inner side becomes the kernel's outer side
+            on = [(ic, oc) for oc, ic in on]
+            norm = [(1 - side, col) for side, col in norm]
+            outer_types, inner_types = inner_types, outer_types
+        self.join_type = LEFT_JOIN if self.swapped else _JOINS[how]
+        self.on = on
+        self.out = norm
+        self.outer_types, self.inner_types = outer_types, inner_types
+        self.out_types = [(inner_types if s else outer_types)[c]
+                          for s, c in norm]
+
+    def to_spec(self):
+        s = BkJoinSpec()
+        s.join_type = self.join_type
+        s.n_keys = len(self.on)
+        for i, (oc, ic) in enumerate(self.on):
+            s.outer_key[i], s.inner_key[i] = oc, ic
+        s.n_out = len(self.out)
+        for i, (side, col) in enumerate(self.out):
+            s.out_side[i], s.out_col[i] = side, col
+        return s

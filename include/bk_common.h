@@ -45,12 +45,29 @@ typedef enum BkNodeType {
     BK_AGG_NODE          = 4,
     BK_MERGE_AGG_NODE    = 5,
     BK_TABLE_FILTER_NODE = 6,
+    BK_JOIN_NODE         = 7,    /* plan.proto:18 */
     BK_LIMIT_NODE        = 11,
     BK_WHERE_FILTER_NODE = 12,
     BK_HAVING_FILTER_NODE = 13,  /* plan.proto:24; a FilterNode whose conjuncts
                                     address the aggregate's output slots */
     BK_WINDOW_NODE       = 42,
 } BkNodeType;
+
+/* ---- pb::JoinType (proto/plan.proto:218-226). The engine builds LEFT, INNER,
+ * SEMI and ANTI_SEMI; a RIGHT join is a LEFT join with the sides swapped
+ * (the caller swaps, as Joiner does, joiner.cpp:134-139); NULL_JOIN and
+ * FULL_JOIN are rejected. ---- */
+typedef enum BkJoinType {
+    BK_NULL_JOIN      = 0,
+    BK_LEFT_JOIN      = 1,
+    BK_RIGHT_JOIN     = 2,
+    BK_INNER_JOIN     = 3,
+    BK_SEMI_JOIN      = 4,
+    BK_ANTI_SEMI_JOIN = 5,
+    BK_FULL_JOIN      = 6,
+} BkJoinType;
+
+#define BK_MAX_JOIN_KEYS 2
 
 /* ---- comparison ops of src/expr/operators.cpp:79-105 (eq/ne/gt/ge/lt/le) ---- */
 typedef enum BkCmpOp {

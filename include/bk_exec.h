@@ -78,6 +78,20 @@ typedef struct BkPlanNodeDesc {
     int32_t     frame_mode;
     int32_t     _pad_w;
     int64_t     frame_pre, frame_fol;
+    /* JOIN_NODE payload (join_node.cpp), APPENDED so that every field above
+     * keeps its offset. The node has two children, each [WHERE ->] SCAN:
+     * child 0 is the outer side, child 1 the inner side; a child's WHERE
+     * restricts that side before the join. Fields as in BkJoinSpec
+     * (bkgpu.h). Above a JOIN_NODE every column index of a node is a
+     * position in this output list. */
+    int32_t     join_type;           /* BkJoinType (RIGHT: swap the children) */
+    int32_t     n_join_keys;
+    int32_t     join_outer_key[BK_MAX_JOIN_KEYS];
+    int32_t     join_inner_key[BK_MAX_JOIN_KEYS];
+    int32_t     n_join_out;
+    int32_t     _pad_j;
+    int32_t     join_out_side[BK_MAX_COLS];   /* 0 outer, 1 inner */
+    int32_t     join_out_col[BK_MAX_COLS];
 } BkPlanNodeDesc;
 
 typedef struct BkExecTree BkExecTree;      /* root ExecNode + RuntimeState */
@@ -105,6 +119,11 @@ int bkexec_open(BkExecTree* t);
  *   WINDOW -> [HAVING ->] AGG -> ...  and  AGG -> [HAVING ->] AGG -> ...
  * The node above drains the aggregate as a device-resident table
  * (bkgpu_agg_to_table); NULL HAVING operands reject the group.
+ * Join plans (each JOIN child is [WHERE ->] SCAN):
+ *   JOIN root: [join output list...], rows in bkgpu_join's result order
+ *   AGG / SORT / WINDOW [-> WHERE] -> JOIN -> (outer child, inner child):
+ *              the node runs over the joined table (bkgpu_join)
+ * num_scan_rows counts both children's scanned rows.
  * Writes row-major into out_tag/out_i/out_d/out_null (capacity*n_slots).
  * Returns rows produced (>=0) and sets *eos, or <0 on error. */
 int64_t bkexec_get_next(BkExecTree* t, int64_t capacity, int32_t* out_tag,

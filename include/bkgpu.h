@@ -210,6 +210,64 @@ void bkgpu_agg_free(BkgAggOut* o);
  * valid and unchanged. NULL on error. */
 BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src, int canonical);
 
+/* ---- equi-join of two HBM tables into a table (JoinNode / Joiner,
+ * src/exec/join_node.cpp, src/exec/joiner.cpp) ----
+ * FROM outer JOIN inner ON outer.k = inner.k [AND outer.k2 = inner.k2].
+ *
+ * join_type: BK_LEFT_JOIN, BK_INNER_JOIN, BK_SEMI_JOIN, BK_ANTI_SEMI_JOIN.
+ *   BK_RIGHT_JOIN is not a kernel mode (swap the sides and run LEFT);
+ *   BK_NULL_JOIN / BK_FULL_JOIN are errors.
+ * Keys: n_keys = 1 or 2 pairs (outer_key[i], inner_key[i]); both columns of
+ *   a pair BK_INT64, or both BK_DATETIME. DOUBLE keys, STRING keys (the dict
+ *   codes of two tables are unrelated) and mismatched pairs are errors.
+ *   Narrow-encoded (bkgpu_table_compact) key columns are fine.
+ * Side filters: q_outer / q_inner (NULL = none) restrict a side BEFORE the
+ *   join; only n_conjuncts / conjuncts / the program pool are read.
+ * NULL keys: a row with a NULL in any key column matches nothing — LEFT
+ *   emits it once NULL-extended, ANTI emits it, INNER and SEMI drop it; a
+ *   NULL-key inner row is never a match candidate.
+ * Row order (deterministic): outer rows that pass the outer filter in
+ *   ascending outer row id; within one outer row its matches in ascending
+ *   inner row id. LEFT emits exactly one NULL-extended row for an outer row
+ *   with no match; SEMI / ANTI emit each qualifying outer row once.
+ * Output columns: out_side[i] (0 = outer, 1 = inner) / out_col[i], n_out in
+ *   1..BK_MAX_COLS; SEMI / ANTI take outer-side entries only. Columns are
+ *   stored wide; an inner-side cell is NULL where the row is NULL-extended
+ *   or the source cell is NULL. A column keeps a validity array only if a
+ *   NULL was written (bkgpu_table_col_nullable), so NULL-free join output
+ *   stays eligible for the SIMPLE / dense routes downstream. BK_STRING
+ *   columns copy codes and the source table's dictionary.
+ * Limits: each table < 2^32 - 1 rows, < 2^31 inner rows passing, < 2^31
+ *   result rows; a larger result is detected from the counts before any
+ *   row-sized output is allocated and is an error. Zero result rows give a
+ *   valid 0-row table.
+ * Returns an ordinary BkgTable (bkgpu_table_free), NULL on error. */
+typedef struct BkJoinSpec {
+    int32_t join_type;                    /* BkJoinType */
+    int32_t n_keys;
+    int32_t outer_key[BK_MAX_JOIN_KEYS];
+    int32_t inner_key[BK_MAX_JOIN_KEYS];
+    int32_t n_out;
+    int32_t out_side[BK_MAX_COLS];        /* 0 outer, 1 inner */
+    int32_t out_col[BK_MAX_COLS];
+} BkJoinSpec;
+BkgTable* bkgpu_join(BkgTable* outer, const BkQuerySpec* q_outer,
+                     BkgTable* inner, const BkQuerySpec* q_inner,
+                     const BkJoinSpec* spec);
+/* The calling thread's last bkgpu_join: out[0] outer rows that passed the
+ * outer filter, out[1] inner rows that passed the inner filter with a
+ * non-NULL key (the build side), out[2] unique build keys, out[3] hash
+ * table slots, out[4] result rows, out[5] route (0 = slots probed in
+ * HBM/L2, 1 = slots copied to LDS), out[6] device time in MICROSECONDS (HIP
+ * events, all stages), out[7] hash table bytes. Returns 0, <0 if the thread
+ * has not joined yet. */
+int bkgpu_join_stats(int64_t out[8]);
+/* per-stage device time (ms, HIP events) of the same join:
+ * {build, count, emit, gather} */
+int bkgpu_join_stage_ms(double out[4]);
+/* outer rows per probe tile (tests place row counts on its edges) */
+int64_t bkgpu_join_tile_rows(void);
+
 /* ---- ORDER BY ... LIMIT top-N ----
  * Select the `limit` smallest rows of [row_begin,row_end) passing q's filter
  * under `order` (INT64/DOUBLE/dict keys, nullable columns ordered per
