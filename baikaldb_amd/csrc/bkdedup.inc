@@ -89,13 +89,6 @@ __global__ void k_dedup_mask(DevCols cols, BkQuerySpec q, int64_t row_begin,
     }
 }
 
-__global__ void k_dedup_iota(uint32_t* v, uint64_t n) {
-    uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += gs)
-        v[i] = (uint32_t)i;
-}
-
 #ifndef BK_DEDUP_MAT_T
 #define BK_DEDUP_MAT_T 16
 #endif
@@ -648,33 +641,18 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
     bool key32 = bits_total + 8 <= 32;
     size_t ksz = key32 ? 4 : 8;
 
+    /* the emit kernel may still be in flight when bufs goes out of scope:
+     * see the INVARIANT at PoolBufs */
+    PoolBufs bufs;
     void *keys = nullptr, *keys2 = nullptr;
-    uint64_t *ctr = nullptr, *rec = nullptr;
+    uint64_t *ctr = nullptr, *rec = nullptr, *mask = nullptr;
     uint32_t *rids = nullptr, *rids2 = nullptr, *f = nullptr, *gidx = nullptr;
-    void* rp_tmp = nullptr;
-    uint64_t* mask_outer = nullptr;   /* set below; freed here */
-    /* INVARIANT (advisor round-1): cleanup() may return buffers that the
-     * emit kernel still references in flight. This is safe ONLY because
-     * every stream this engine creates is blocking w.r.t. the null stream
-     * and pool_free merely recycles within this process's pool — any
-     * reuse is ordered behind the in-flight kernel by stream semantics.
-     * If a non-blocking stream or async allocator is ever introduced,
-     * synchronize before cleanup() here. */
-    auto cleanup = [&]() {
-        pool_free(keys); pool_free(keys2); pool_free(ctr); pool_free(rids);
-        pool_free(rids2); pool_free(f); pool_free(gidx); pool_free(rp_tmp);
-        pool_free(rec); pool_free(mask_outer);
-    };
-    #define DCHECK(x) do { if ((x) != hipSuccess) { \
-        snprintf(g_err, sizeof g_err, "sorted %s:%d %s", __FILE__, __LINE__, \
-                 hipGetErrorString(hipGetLastError())); cleanup(); \
-        return nullptr; } } while (0)
-    DCHECK(pool_alloc(&keys, (size_t)range * ksz));
-    DCHECK(pool_alloc((void**)&rids, (size_t)range * 4));
+    BK_TRY("sorted", bufs.get(&keys, (size_t)range * ksz), nullptr);
+    BK_TRY("sorted", bufs.get(&rids, (size_t)range * 4), nullptr);
     if (recmode)
-        DCHECK(pool_alloc((void**)&rec, (size_t)range * lay.nwords * 8));
-    DCHECK(pool_alloc((void**)&ctr, 8));
-    DCHECK(hipMemset(ctr, 0, 8));
+        BK_TRY("sorted", bufs.get(&rec, (size_t)range * lay.nwords * 8), nullptr);
+    BK_TRY("sorted", bufs.get(&ctr, 8), nullptr);
+    BK_TRY("sorted", hipMemset(ctr, 0, 8), nullptr);
 
     static const char* NAMESD[] = {"dedup_mat", "sort", "scan", "emit"};
     EvTimer tm;
@@ -706,14 +684,10 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
      * gains nothing over the fused loop's batched loads, so the second
      * pass's mask+key reads are pure overhead. Kept behind BK_MAT_SPLIT
      * for re-testing. */
-    uint64_t*& mask = mask_outer;
     bool split = q->n_conjuncts > 0 && range >= 30 * 1000 * 1000 &&
                  getenv("BK_MAT_SPLIT") != nullptr;
-    if (split) {
-        if (pool_alloc((void**)&mask,
-                       ((size_t)range + 63) / 64 * 8) != hipSuccess)
-            split = false;
-    }
+    if (split && bufs.get(&mask, ((size_t)range + 63) / 64 * 8) != hipSuccess)
+        split = false;
     {
         if (split) {
             if (simple)
@@ -791,60 +765,40 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
         #undef MAT_PICK
         #undef MAT_LAUNCH
     }
-    DCHECK(hipGetLastError());
+    BK_TRY("sorted", hipGetLastError(), nullptr);
     uint64_t n = 0;
-    DCHECK(hipMemcpy(&n, ctr, 8, hipMemcpyDeviceToHost));
+    BK_TRY("sorted", hipMemcpy(&n, ctr, 8, hipMemcpyDeviceToHost), nullptr);
     tm.record();
 
     uint64_t ngroups = 0;
     if (n > 0) {
-        DCHECK(pool_alloc(&keys2, (size_t)n * ksz));
-        DCHECK(pool_alloc((void**)&rids2, (size_t)n * 4));
+        BK_TRY("sorted", bufs.get(&keys2, (size_t)n * ksz), nullptr);
+        BK_TRY("sorted", bufs.get(&rids2, (size_t)n * 4), nullptr);
         if (recmode)   /* sort values = record indices */
-            hipLaunchKernelGGL(k_dedup_iota, dim3(2048), dim3(256), 0, 0,
-                               rids, n);
-        size_t rp_bytes = 0;
-        if (key32) {
-            DCHECK(rocprim::radix_sort_pairs(nullptr, rp_bytes,
-                                             (uint32_t*)keys, (uint32_t*)keys2,
-                                             rids, rids2, (size_t)n, 0,
-                                             (unsigned)(bits_total + 8)));
-            DCHECK(pool_alloc(&rp_tmp, rp_bytes));
-            DCHECK(rocprim::radix_sort_pairs(rp_tmp, rp_bytes,
-                                             (uint32_t*)keys, (uint32_t*)keys2,
-                                             rids, rids2, (size_t)n, 0,
-                                             (unsigned)(bits_total + 8)));
-        } else {
-            DCHECK(rocprim::radix_sort_pairs(nullptr, rp_bytes,
-                                             (uint64_t*)keys, (uint64_t*)keys2,
-                                             rids, rids2, (size_t)n, 0,
-                                             (unsigned)(bits_total + 8)));
-            DCHECK(pool_alloc(&rp_tmp, rp_bytes));
-            DCHECK(rocprim::radix_sort_pairs(rp_tmp, rp_bytes,
-                                             (uint64_t*)keys, (uint64_t*)keys2,
-                                             rids, rids2, (size_t)n, 0,
-                                             (unsigned)(bits_total + 8)));
-        }
+            dev_iota(rids, n, 2048);
+        const unsigned end_bit = (unsigned)(bits_total + 8);
+        if (key32)
+            BK_TRY("sorted", dev_sort_pairs(bufs, (uint32_t*)keys, (uint32_t*)keys2,
+                                            rids, rids2, (size_t)n, 0, end_bit),
+                   nullptr);
+        else
+            BK_TRY("sorted", dev_sort_pairs(bufs, (uint64_t*)keys, (uint64_t*)keys2,
+                                            rids, rids2, (size_t)n, 0, end_bit),
+                   nullptr);
         tm.record();
-        DCHECK(pool_alloc((void**)&f, (size_t)n * 4));
-        DCHECK(pool_alloc((void**)&gidx, (size_t)n * 4));
+        BK_TRY("sorted", bufs.get(&f, (size_t)n * 4), nullptr);
+        BK_TRY("sorted", bufs.get(&gidx, (size_t)n * 4), nullptr);
         if (key32)
             hipLaunchKernelGGL(k_dedup_heads<uint32_t>, dim3(2048), dim3(256),
                                0, 0, (const uint32_t*)keys2, n, f);
         else
             hipLaunchKernelGGL(k_dedup_heads<uint64_t>, dim3(2048), dim3(256),
                                0, 0, (const uint64_t*)keys2, n, f);
-        size_t sc_bytes = 0;
-        DCHECK(rocprim::inclusive_scan(nullptr, sc_bytes, f, gidx, (size_t)n,
-                                       rocprim::plus<uint32_t>()));
-        if (sc_bytes > rp_bytes) {
-            pool_free(rp_tmp); rp_tmp = nullptr;
-            DCHECK(pool_alloc(&rp_tmp, sc_bytes));
-        }
-        DCHECK(rocprim::inclusive_scan(rp_tmp, sc_bytes, f, gidx, (size_t)n,
-                                       rocprim::plus<uint32_t>()));
+        BK_TRY("sorted", dev_inclusive_scan(bufs, f, gidx, (size_t)n,
+                                            DevPlus<uint32_t>()), nullptr);
         uint32_t ng32 = 0;
-        DCHECK(hipMemcpy(&ng32, gidx + (n - 1), 4, hipMemcpyDeviceToHost));
+        BK_TRY("sorted", hipMemcpy(&ng32, gidx + (n - 1), 4, hipMemcpyDeviceToHost),
+               nullptr);
         ngroups = ng32;
     } else {
         tm.record();
@@ -854,12 +808,14 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
     BkgAggOut* o = new BkgAggOut();
     o->q = *q;
     if (agg_alloc(o, std::max<int64_t>(1, (int64_t)ngroups)) != 0) {
-        cleanup(); bkgpu_agg_free(o); return nullptr;
+        bkgpu_agg_free(o); return nullptr;
     }
     /* dense table: fill = ngroups (merge's capacity check then always
      * rebuilds to a hash table first), rows_passed = survivors */
-    DCHECK(hipMemcpy(o->ctrs, &ngroups, 8, hipMemcpyHostToDevice));
-    DCHECK(hipMemcpy(o->ctrs + 1, &n, 8, hipMemcpyHostToDevice));
+    BK_TRY("sorted", hipMemcpy(o->ctrs, &ngroups, 8, hipMemcpyHostToDevice),
+           (bkgpu_agg_free(o), nullptr));
+    BK_TRY("sorted", hipMemcpy(o->ctrs + 1, &n, 8, hipMemcpyHostToDevice),
+           (bkgpu_agg_free(o), nullptr));
     if (n > 0) {
         #define EMIT_LAUNCH(NAv, K, R)                                       \
             hipLaunchKernelGGL((k_dedup_emit<NAv, K, R>), dim3(4096),        \
@@ -879,17 +835,10 @@ extern "C" BkgAggOut* bkgpu_filter_agg_sorted(BkgTable* t, const BkQuerySpec* q,
                            else EMIT_LAUNCH(8, uint64_t, false); }
         }
         #undef EMIT_LAUNCH
-        hipError_t lerr = hipGetLastError();
-        if (lerr != hipSuccess) {
-            snprintf(g_err, sizeof g_err, "dedup_emit launch: %s",
-                     hipGetErrorString(lerr));
-            cleanup(); bkgpu_agg_free(o); return nullptr;
-        }
+        BK_TRY("sorted", hipGetLastError(), (bkgpu_agg_free(o), nullptr));
     }
     tm.record();
     tm.finish(o, NAMESD);
-    #undef DCHECK
-    cleanup();
     o->dirty = true;
     o->rows_passed = (int64_t)n;   /* compaction stays lazy (see filter_agg) */
     return o;

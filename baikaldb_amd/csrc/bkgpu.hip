@@ -2069,6 +2069,7 @@ static DevCols table_cols(const BkgTable* t);
 static hipError_t pool_alloc(void** p, size_t bytes);
 static void pool_free(void* p);
 static size_t elem_size(int32_t t);
+static hipError_t col_alloc(void** p, int64_t n, size_t es);
 static int ensure_device();
 
 static int ensure_stats(BkgTable* t, int col) {
@@ -2154,7 +2155,7 @@ static int widen_col(BkgTable* t, int c) {
         return 0;
     }
     void* nd = nullptr;
-    if (hipMalloc(&nd, (size_t)t->nrows * es + 16) != hipSuccess) {
+    if (col_alloc(&nd, t->nrows, es) != hipSuccess) {
         set_err("widen_col: oom");
         return -1;
     }
@@ -2209,7 +2210,7 @@ extern "C" int bkgpu_table_compact(BkgTable* t, int col) {
                   : range <= 0xFFFFFFFFull ? 4 : 8;
         if (tgt >= cur) continue;
         void* nd = nullptr;
-        if (hipMalloc(&nd, (size_t)t->nrows * tgt + 16) != hipSuccess) continue;
+        if (col_alloc(&nd, t->nrows, (size_t)tgt) != hipSuccess) continue;
         switch (tgt) {
             case 1:
                 hipLaunchKernelGGL(k_narrow_col<uint8_t>, dim3(2048),
@@ -2362,6 +2363,43 @@ static size_t elem_size(int32_t t) {
     }
 }
 
+/* the one place a table column is sized: n cells plus the 16-byte tail pad
+ * that cell_i64's unaligned 8-byte load and the 16-byte vector loads of
+ * k_dedup_mat_vec may read past the last cell */
+static hipError_t col_alloc(void** p, int64_t n, size_t es) {
+    return hipMalloc(p, (size_t)n * es + 16);
+}
+
+/* column `col` of t: spec type, natural width, data of n cells and, when
+ * want_valid, a validity byte per row */
+static hipError_t table_alloc_col(BkgTable* t, int col, int32_t type, int64_t n,
+                                  bool want_valid) {
+    const size_t es = elem_size(type);
+    if (es == 0) return hipErrorInvalidValue;
+    t->specs[col].col_type = type;
+    t->width[col] = (uint8_t)es;
+    hipError_t e = col_alloc(&t->data[col], n, es);
+    if (e == hipSuccess && want_valid)
+        e = hipMalloc((void**)&t->valid[col], (size_t)n);
+    return e;
+}
+
+/* keep validity only where a NULL was seen (a NULL-free column stays
+ * eligible for the SIMPLE / dense / sort-dedup routes downstream) and carry
+ * the dictionary of a STRING column over from src_table's src_col */
+static void table_trim_validity(BkgTable* t, int col, bool saw_null,
+                                const BkgTable* src_table, int src_col) {
+    if (saw_null) {
+        t->specs[col].null_frac_x1e6 = 1;
+    } else if (t->valid[col]) {
+        (void)hipFree(t->valid[col]);
+        t->valid[col] = nullptr;
+    }
+    if (t->specs[col].col_type == BK_STRING && src_table && src_col >= 0 &&
+        src_col < src_table->ncols && src_table->dict[src_col])
+        t->dict[col] = new std::vector<std::string>(*src_table->dict[src_col]);
+}
+
 extern "C" BkgTable* bkgpu_table_create(int ncols, const BkColSpec* specs,
                                         int64_t nrows) {
     if (ensure_device() != 0) return nullptr;
@@ -2374,7 +2412,7 @@ extern "C" BkgTable* bkgpu_table_create(int ncols, const BkColSpec* specs,
         size_t es = elem_size(specs[c].col_type);
         if (es == 0) { set_err("unsupported col type"); delete t; return nullptr; }
         t->width[c] = (uint8_t)es;
-        if (hipMalloc(&t->data[c], (size_t)nrows * es + 16) != hipSuccess) {
+        if (col_alloc(&t->data[c], nrows, es) != hipSuccess) {
             set_err("hipMalloc column failed");
             bkgpu_table_free(t);
             return nullptr;
@@ -2577,7 +2615,7 @@ extern "C" int bkgpu_table_derive_remap(BkgTable* t, int src_col,
     int nc = t->ncols;
     int32_t* dcol = nullptr;
     int32_t* dremap = nullptr;
-    HIP_CHECK(hipMalloc((void**)&dcol, (size_t)t->nrows * 4 + 16));
+    HIP_CHECK(col_alloc((void**)&dcol, t->nrows, 4));
     if (hipMalloc((void**)&dremap, (size_t)ncodes * 4) != hipSuccess) {
         (void)hipFree(dcol);
         set_err("derive_remap: oom");
@@ -2670,7 +2708,7 @@ extern "C" int bkgpu_table_derive_prog(BkgTable* t, const BkExprOp* prog,
     int nc = t->ncols;
     void* dcol = nullptr;
     uint8_t* dval = nullptr;
-    HIP_CHECK(hipMalloc(&dcol, (size_t)t->nrows * 8 + 16));
+    HIP_CHECK(col_alloc(&dcol, t->nrows, 8));
     if (nullable &&
         hipMalloc((void**)&dval, (size_t)t->nrows) != hipSuccess) {
         (void)hipFree(dcol);
@@ -4133,6 +4171,7 @@ extern "C" int bkgpu_gather(BkgTable* t, int col, const int64_t* rowids_host,
     return 0;
 }
 
+#include "bkprim.inc"
 #include "bksort.inc"
 #include "bkwin.inc"
 #include "bkdedup.inc"

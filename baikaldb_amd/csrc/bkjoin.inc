@@ -1,7 +1,10 @@
 // bkjoin.inc — equi-join of two HBM tables into a table (bkgpu_join,
 // include/bkgpu.h): the device form of JoinNode's hash join
 // (src/exec/join_node.cpp, src/exec/joiner.cpp). Included from bkgpu.hip
-// (shares BkgTable / DevCol / key_hash / the pool / k_dedup_mask / k_iota).
+// (shares BkgTable / DevCol / key_hash / k_dedup_mask; the host side is built
+// from bkprim.inc — PoolBufs, BK_TRY, launch_grid, dev_*_scan,
+// dev_lsd_perm_sort — and the table-column helpers next to
+// bkgpu_table_create: table_alloc_col, table_trim_validity).
 //
 // Build side (inner): filter mask (k_dedup_mask) + key-non-NULL -> ordered
 // compaction to (key words, inner row id) -> one stable rocPRIM radix pass
@@ -125,14 +128,15 @@ k_join_bcompact(DevCol k0, DevCol k1, const uint32_t* __restrict__ flag,
     }
 }
 
-/* sort key of one radix pass: out[i] = ck[perm[i]] */
+/* sort key of one radix pass: out[i] = ck[perm[i]] (perm == nullptr on the
+ * first pass: identity) */
 __global__ void __launch_bounds__(256)
 k_join_permkey(const uint64_t* __restrict__ ck, const uint32_t* __restrict__ perm,
                uint64_t n, uint64_t* __restrict__ out) {
     const uint64_t gs = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
          i += gs)
-        out[i] = ck[perm[i]];
+        out[i] = ck[perm ? perm[i] : i];
 }
 
 /* after the sort: srid[i] = inner row id at sorted position i, head[i] = a
@@ -407,28 +411,8 @@ k_join_gather(DevCol c, const uint32_t* __restrict__ rid, int64_t n,
 
 /* ---- host ---- */
 
-/* pool buffers of one join, returned on every exit path. Safe while kernels
- * that reference them are still queued: everything here runs on the null
- * stream (the pool's reuse invariant, see pool_free). */
-struct JoinBufs {
-    std::vector<void*> v;
-    template <class T> bool get(T** p, size_t bytes) {
-        void* q = nullptr;
-        if (pool_alloc(&q, bytes ? bytes : 16) != hipSuccess) return false;
-        v.push_back(q);
-        *p = (T*)q;
-        return true;
-    }
-    ~JoinBufs() { for (void* p : v) pool_free(p); }
-};
-
-static unsigned join_grid(uint64_t n, unsigned per_block = 256, unsigned cap = 2048) {
-    uint64_t b = (n + per_block - 1) / per_block;
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(b, cap));
-}
-
 /* side filter -> 1 bit per row (nullptr = every row passes) */
-static int join_side_mask(BkgTable* t, const BkQuerySpec* q, JoinBufs& bufs,
+static int join_side_mask(BkgTable* t, const BkQuerySpec* q, PoolBufs& bufs,
                           uint64_t** mask, const char* side) {
     *mask = nullptr;
     if (!q || q->n_conjuncts == 0 || t->nrows == 0) return 0;
@@ -448,15 +432,15 @@ static int join_side_mask(BkgTable* t, const BkQuerySpec* q, JoinBufs& bufs,
     }
     if (query_exprs_check(t, q) != 0) return -1;
     const size_t words = ((size_t)t->nrows + 63) / 64;
-    if (!bufs.get(mask, words * 8)) { set_err("join: mask alloc failed"); return -1; }
+    BK_TRY("join", bufs.get(mask, words * 8), -1);
     /* only the filter part of the spec reaches the mask kernel */
     BkQuerySpec qf = *q;
     qf.n_group = 0;
     qf.n_aggs = 0;
-    hipLaunchKernelGGL(k_dedup_mask<false>, dim3(join_grid(t->nrows, 512, 8192)),
+    hipLaunchKernelGGL(k_dedup_mask<false>, dim3(launch_grid(t->nrows, 512, 8192)),
                        dim3(512), 0, 0, table_cols(t), qf, (int64_t)0, t->nrows,
                        *mask);
-    if (hipGetLastError() != hipSuccess) { set_err("join: mask kernel failed"); return -1; }
+    BK_TRY("join", hipGetLastError(), -1);
     return 0;
 }
 
@@ -529,20 +513,15 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
     constexpr int W = NK + 1;
     const int jt = s->join_type;
     const bool pairs = jt == BK_INNER_JOIN || jt == BK_LEFT_JOIN;
-    JoinBufs bufs;
+    PoolBufs bufs;
     JoinStats st;
     const DevCols oc = table_cols(outer), ic = table_cols(inner);
     const DevCol ok0 = oc.c[s->outer_key[0]], ok1 = oc.c[s->outer_key[NK - 1]];
     const DevCol ik0 = ic.c[s->inner_key[0]], ik1 = ic.c[s->inner_key[NK - 1]];
-    #define JCHECK(x, what) do { if ((x) != hipSuccess) {                      \
-        snprintf(g_err, sizeof g_err, "join: %s: %s", what,                    \
-                 hipGetErrorString(hipGetLastError())); return nullptr; } } while (0)
-    #define JALLOC(p, bytes) do { if (!bufs.get(&(p), (bytes))) {              \
-        set_err("join: temporary allocation failed"); return nullptr; } } while (0)
 
-    hipEvent_t ev[5];
-    for (auto& e : ev) JCHECK(hipEventCreate(&e), "event create");
-    struct EvFree { hipEvent_t* e; ~EvFree() { for (int i = 0; i < 5; i++) (void)hipEventDestroy(e[i]); } } evfree{ev};
+    DevEvents<5> evs;
+    hipEvent_t* ev = evs.e;
+    BK_TRY("join", evs.create(), nullptr);
     (void)hipEventRecord(ev[0]);
 
     uint64_t *omask = nullptr, *imask = nullptr;
@@ -552,22 +531,15 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
     /* ---- build ---- */
     const int64_t ni = inner->nrows;
     uint32_t *flag = nullptr, *pos = nullptr;
-    void* rp_tmp = nullptr;
-    size_t rp_bytes = 0;
-    JALLOC(flag, (size_t)(ni + 1) * 4);
-    JALLOC(pos, (size_t)(ni + 1) * 4);
-    hipLaunchKernelGGL(k_join_bflag<NK>, dim3(join_grid(ni + 1)), dim3(256), 0, 0,
+    BK_TRY("join", bufs.get(&flag, (size_t)(ni + 1) * 4), nullptr);
+    BK_TRY("join", bufs.get(&pos, (size_t)(ni + 1) * 4), nullptr);
+    hipLaunchKernelGGL(k_join_bflag<NK>, dim3(launch_grid(ni + 1)), dim3(256), 0, 0,
                        ik0, ik1, imask, ni, flag);
-    JCHECK(hipGetLastError(), "build flag kernel");
-    JCHECK(rocprim::exclusive_scan(nullptr, rp_bytes, flag, pos, 0u,
-                                   (size_t)(ni + 1), rocprim::plus<uint32_t>()),
-           "build scan size");
-    JALLOC(rp_tmp, rp_bytes);
-    JCHECK(rocprim::exclusive_scan(rp_tmp, rp_bytes, flag, pos, 0u,
-                                   (size_t)(ni + 1), rocprim::plus<uint32_t>()),
-           "build scan");
+    BK_TRY("join", hipGetLastError(), nullptr);
+    BK_TRY("join", dev_exclusive_scan(bufs, flag, pos, 0u, (size_t)(ni + 1),
+                                      DevPlus<uint32_t>()), nullptr);
     uint32_t nb32 = 0;
-    JCHECK(hipMemcpy(&nb32, pos + ni, 4, hipMemcpyDeviceToHost), "build count");
+    BK_TRY("join", hipMemcpy(&nb32, pos + ni, 4, hipMemcpyDeviceToHost), nullptr);
     const uint64_t nb = nb32;
     if (nb >= (1ull << 31)) {
         set_err("join: the inner side holds >= 2^31 passing rows");
@@ -577,63 +549,46 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
     uint32_t *crid = nullptr, *perm = nullptr, *srid = nullptr, *ustart = nullptr;
     uint32_t nuniq = 0;
     if (nb > 0) {
-        uint32_t *perm2 = nullptr, *head = nullptr, *uidx = nullptr;
-        uint64_t *sk = nullptr, *sk2 = nullptr;
-        JALLOC(ck0, nb * 8);
-        if (NK == 2) JALLOC(ck1, nb * 8);
-        JALLOC(crid, nb * 4);
-        JALLOC(perm, nb * 4);
-        JALLOC(perm2, nb * 4);
-        JALLOC(sk, nb * 8);
-        JALLOC(sk2, nb * 8);
-        JALLOC(srid, nb * 4);
-        JALLOC(head, nb * 4);
-        JALLOC(uidx, nb * 4);
-        hipLaunchKernelGGL(k_join_bcompact<NK>, dim3(join_grid(ni)), dim3(256), 0,
+        uint32_t *head = nullptr, *uidx = nullptr;
+        BK_TRY("join", bufs.get(&ck0, nb * 8), nullptr);
+        if (NK == 2) BK_TRY("join", bufs.get(&ck1, nb * 8), nullptr);
+        BK_TRY("join", bufs.get(&crid, nb * 4), nullptr);
+        BK_TRY("join", bufs.get(&srid, nb * 4), nullptr);
+        BK_TRY("join", bufs.get(&head, nb * 4), nullptr);
+        BK_TRY("join", bufs.get(&uidx, nb * 4), nullptr);
+        hipLaunchKernelGGL(k_join_bcompact<NK>, dim3(launch_grid(ni)), dim3(256), 0,
                            0, ik0, ik1, flag, pos, ni, ck0, ck1, crid);
-        hipLaunchKernelGGL(k_iota, dim3(join_grid(nb)), dim3(256), 0, 0, perm, nb);
-        JCHECK(hipGetLastError(), "build compact kernel");
-        size_t so_bytes = 0;
-        JCHECK(rocprim::radix_sort_pairs(nullptr, so_bytes, sk, sk2, perm, perm2,
-                                         (size_t)nb, 0, 64), "sort size");
-        void* so_tmp = nullptr;
-        JALLOC(so_tmp, so_bytes);
+        BK_TRY("join", hipGetLastError(), nullptr);
         /* stable LSD passes, last key first: equal keys adjacent, compacted
          * indices (hence inner row ids) ascending inside a run */
-        for (int k = NK - 1; k >= 0; k--) {
-            hipLaunchKernelGGL(k_join_permkey, dim3(join_grid(nb)), dim3(256), 0,
-                               0, k == 0 ? ck0 : ck1, perm, nb, sk);
-            JCHECK(hipGetLastError(), "sort key kernel");
-            JCHECK(rocprim::radix_sort_pairs(so_tmp, so_bytes, sk, sk2, perm,
-                                             perm2, (size_t)nb, 0, 64), "sort");
-            std::swap(perm, perm2);
-        }
-        hipLaunchKernelGGL(k_join_heads<NK>, dim3(join_grid(nb)), dim3(256), 0, 0,
+        perm = dev_lsd_perm_sort(
+            bufs, nb, NK, [](int) { return 64; },
+            [&](int pass, const uint32_t* p, uint64_t* keys) {
+                hipLaunchKernelGGL(k_join_permkey, dim3(launch_grid(nb)), dim3(256),
+                                   0, 0, pass == NK - 1 ? ck0 : ck1, p, nb, keys);
+            }, launch_grid(nb));
+        if (!perm) return nullptr;
+        hipLaunchKernelGGL(k_join_heads<NK>, dim3(launch_grid(nb)), dim3(256), 0, 0,
                            ck0, ck1, crid, perm, nb, srid, head);
-        JCHECK(hipGetLastError(), "heads kernel");
-        size_t sc_bytes = 0;
-        JCHECK(rocprim::inclusive_scan(nullptr, sc_bytes, head, uidx, (size_t)nb,
-                                       rocprim::plus<uint32_t>()), "run scan size");
-        void* sc_tmp = nullptr;
-        JALLOC(sc_tmp, sc_bytes);
-        JCHECK(rocprim::inclusive_scan(sc_tmp, sc_bytes, head, uidx, (size_t)nb,
-                                       rocprim::plus<uint32_t>()), "run scan");
-        JCHECK(hipMemcpy(&nuniq, uidx + (nb - 1), 4, hipMemcpyDeviceToHost),
-               "unique count");
-        JALLOC(ustart, ((size_t)nuniq + 1) * 4);
-        hipLaunchKernelGGL(k_join_runs, dim3(join_grid(nb + 1)), dim3(256), 0, 0,
+        BK_TRY("join", hipGetLastError(), nullptr);
+        BK_TRY("join", dev_inclusive_scan(bufs, head, uidx, (size_t)nb,
+                                          DevPlus<uint32_t>()), nullptr);
+        BK_TRY("join", hipMemcpy(&nuniq, uidx + (nb - 1), 4, hipMemcpyDeviceToHost),
+               nullptr);
+        BK_TRY("join", bufs.get(&ustart, ((size_t)nuniq + 1) * 4), nullptr);
+        hipLaunchKernelGGL(k_join_runs, dim3(launch_grid(nb + 1)), dim3(256), 0, 0,
                            head, uidx, nb, nuniq, ustart);
-        JCHECK(hipGetLastError(), "runs kernel");
+        BK_TRY("join", hipGetLastError(), nullptr);
     }
     const uint64_t nslots = (uint64_t)std::max<int64_t>(16, next_pow2(2 * (int64_t)nuniq));
     const size_t slot_bytes = (size_t)nslots * W * 8;
     uint64_t* slots = nullptr;
-    JALLOC(slots, slot_bytes);
-    JCHECK(hipMemsetAsync(slots, 0, slot_bytes, 0), "slot clear");
+    BK_TRY("join", bufs.get(&slots, slot_bytes), nullptr);
+    BK_TRY("join", hipMemsetAsync(slots, 0, slot_bytes, 0), nullptr);
     if (nuniq > 0) {
-        hipLaunchKernelGGL(k_join_insert<NK>, dim3(join_grid(nuniq)), dim3(256), 0,
+        hipLaunchKernelGGL(k_join_insert<NK>, dim3(launch_grid(nuniq)), dim3(256), 0,
                            0, ck0, ck1, perm, ustart, nuniq, slots, nslots - 1);
-        JCHECK(hipGetLastError(), "insert kernel");
+        BK_TRY("join", hipGetLastError(), nullptr);
     }
     (void)hipEventRecord(ev[1]);
 
@@ -655,9 +610,9 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
     const unsigned pgrid = (unsigned)std::max<int64_t>(
         1, std::min<int64_t>(ntiles, (int64_t)256 * per_cu));
     uint64_t *tile_tot = nullptr, *tile_base = nullptr;
-    JALLOC(tile_tot, (size_t)(ntiles + 1) * 8);
-    JALLOC(tile_base, (size_t)(ntiles + 1) * 8);
-    JCHECK(hipMemsetAsync(tile_tot + ntiles, 0, 8, 0), "tile clear");
+    BK_TRY("join", bufs.get(&tile_tot, (size_t)(ntiles + 1) * 8), nullptr);
+    BK_TRY("join", bufs.get(&tile_base, (size_t)(ntiles + 1) * 8), nullptr);
+    BK_TRY("join", hipMemsetAsync(tile_tot + ntiles, 0, 8, 0), nullptr);
     auto count_fn = lds ? k_join_count<NK, true> : k_join_count<NK, false>;
     auto emit_fn = lds ? k_join_emit<NK, true> : k_join_emit<NK, false>;
     if (lds && smem > 64 * 1024) {
@@ -669,30 +624,24 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
     if (ntiles > 0) {
         hipLaunchKernelGGL(count_fn, dim3(pgrid), dim3(JOIN_BS), smem, 0, ok0, ok1,
                            omask, no, jt, slots, nslots, ntiles, tile_tot);
-        JCHECK(hipGetLastError(), "count kernel");
+        BK_TRY("join", hipGetLastError(), nullptr);
     }
-    size_t ts_bytes = 0;
-    JCHECK(rocprim::exclusive_scan(nullptr, ts_bytes, tile_tot, tile_base,
-                                   (uint64_t)0, (size_t)(ntiles + 1),
-                                   rocprim::plus<uint64_t>()), "tile scan size");
-    void* ts_tmp = nullptr;
-    JALLOC(ts_tmp, ts_bytes);
-    JCHECK(rocprim::exclusive_scan(ts_tmp, ts_bytes, tile_tot, tile_base,
-                                   (uint64_t)0, (size_t)(ntiles + 1),
-                                   rocprim::plus<uint64_t>()), "tile scan");
+    BK_TRY("join", dev_exclusive_scan(bufs, tile_tot, tile_base, (uint64_t)0,
+                                      (size_t)(ntiles + 1), DevPlus<uint64_t>()),
+           nullptr);
     /* passing outer rows, for the stats only */
     unsigned long long* d_pass = nullptr;
-    JALLOC(d_pass, 8);
-    JCHECK(hipMemsetAsync(d_pass, 0, 8, 0), "counter clear");
+    BK_TRY("join", bufs.get(&d_pass, 8), nullptr);
+    BK_TRY("join", hipMemsetAsync(d_pass, 0, 8, 0), nullptr);
     if (omask)
-        hipLaunchKernelGGL(k_join_popc, dim3(join_grid(((uint64_t)no + 63) / 64)),
+        hipLaunchKernelGGL(k_join_popc, dim3(launch_grid(((uint64_t)no + 63) / 64)),
                            dim3(256), 0, 0, omask, ((uint64_t)no + 63) / 64, d_pass);
     uint64_t total = 0;
     unsigned long long opass = 0;
     /* the one host wait of the probe: the result size */
-    JCHECK(hipMemcpy(&total, tile_base + ntiles, 8, hipMemcpyDeviceToHost),
-           "result size");
-    JCHECK(hipMemcpy(&opass, d_pass, 8, hipMemcpyDeviceToHost), "pass count");
+    BK_TRY("join", hipMemcpy(&total, tile_base + ntiles, 8, hipMemcpyDeviceToHost),
+           nullptr);
+    BK_TRY("join", hipMemcpy(&opass, d_pass, 8, hipMemcpyDeviceToHost), nullptr);
     if (!omask) opass = (unsigned long long)no;
     (void)hipEventRecord(ev[2]);
     if (total >= (1ull << 31)) {
@@ -705,13 +654,13 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
     /* ---- probe pass 2 ---- */
     const int64_t n = (int64_t)total;
     uint32_t *orid = nullptr, *irid = nullptr;
-    JALLOC(orid, (size_t)n * 4);
-    if (pairs) JALLOC(irid, (size_t)n * 4);
+    BK_TRY("join", bufs.get(&orid, (size_t)n * 4), nullptr);
+    if (pairs) BK_TRY("join", bufs.get(&irid, (size_t)n * 4), nullptr);
     if (n > 0) {
         hipLaunchKernelGGL(emit_fn, dim3(pgrid), dim3(JOIN_BS), smem, 0, ok0, ok1,
                            omask, no, jt, slots, nslots, ntiles, tile_base, srid,
                            total, orid, irid);
-        JCHECK(hipGetLastError(), "emit kernel");
+        BK_TRY("join", hipGetLastError(), nullptr);
     }
     (void)hipEventRecord(ev[3]);
 
@@ -721,23 +670,19 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
     t->nrows = n;
     uint32_t* d_null = nullptr;
     uint32_t h_null = 0;
-    bool ok = bufs.get(&d_null, 4) && hipMemsetAsync(d_null, 0, 4, 0) == hipSuccess;
+    bool ok = bufs.get(&d_null, 4) == hipSuccess &&
+              hipMemsetAsync(d_null, 0, 4, 0) == hipSuccess;
+    if (!ok) set_err("join: null-mask allocation failed");
     for (int col = 0; ok && col < s->n_out; col++) {
         const bool in_side = s->out_side[col] == 1;
         const BkgTable* src = in_side ? inner : outer;
         const int sc = s->out_col[col];
-        const int32_t ty = src->specs[sc].col_type;
-        const size_t es = elem_size(ty);
-        t->specs[col] = BkColSpec{};
-        t->specs[col].col_type = ty;
-        t->width[col] = (uint8_t)es;
-        /* stored wide, with the 16-byte tail pad every column carries */
-        ok = es != 0 && hipMalloc(&t->data[col], (size_t)n * es + 16) == hipSuccess;
-        /* a NULL can only come from a nullable source or a NULL extension */
+        /* stored wide; a NULL can only come from a nullable source or a NULL
+         * extension */
         const bool may_null = src->valid[sc] != nullptr ||
                               (in_side && jt == BK_LEFT_JOIN);
-        if (ok && may_null && n > 0)
-            ok = hipMalloc((void**)&t->valid[col], (size_t)n) == hipSuccess;
+        ok = table_alloc_col(t, col, src->specs[sc].col_type, n,
+                             may_null && n > 0) == hipSuccess;
         if (!ok) { set_err("join: hipMalloc of an output column failed"); break; }
         if (n > 0) {
             hipLaunchKernelGGL(k_join_gather, dim3((unsigned)((n + 255) / 256)),
@@ -758,19 +703,9 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
         bkgpu_table_free(t);
         return nullptr;
     }
-    for (int col = 0; col < s->n_out; col++) {
-        /* keep validity only where a NULL was written */
-        if ((h_null >> col) & 1) {
-            t->specs[col].null_frac_x1e6 = 1;
-        } else if (t->valid[col]) {
-            (void)hipFree(t->valid[col]);
-            t->valid[col] = nullptr;
-        }
-        const BkgTable* src = s->out_side[col] ? inner : outer;
-        const int sc = s->out_col[col];
-        if (t->specs[col].col_type == BK_STRING && src->dict[sc])
-            t->dict[col] = new std::vector<std::string>(*src->dict[sc]);
-    }
+    for (int col = 0; col < s->n_out; col++)
+        table_trim_validity(t, col, (h_null >> col) & 1,
+                            s->out_side[col] ? inner : outer, s->out_col[col]);
     double tot_ms = 0;
     for (int i = 0; i < 4; i++) {
         float ms = 0.f;
@@ -794,8 +729,6 @@ static BkgTable* join_run(BkgTable* outer, const BkQuerySpec* q_outer,
                 (unsigned long long)nb, nuniq, (unsigned long long)nslots,
                 lds ? "lds" : "global", (long long)n, st.stage_ms[0],
                 st.stage_ms[1], st.stage_ms[2], st.stage_ms[3]);
-    #undef JCHECK
-    #undef JALLOC
     return t;
 }
 

@@ -2,7 +2,8 @@
 // an HBM-resident BkgTable of FINALIZED values, so HAVING (the filter),
 // ORDER BY/LIMIT (top-N), window functions and re-aggregation run over
 // GROUP BY output with the kernels they already have. Included from
-// bkgpu.hip (shares BkgTable / BkgAggOut / agg_compact / the pool).
+// bkgpu.hip (shares BkgTable / BkgAggOut / agg_compact, bkprim.inc and the
+// table-column helpers).
 //
 // Source: the compact wire blob (agg_compact) — every result form (hash
 // table, dense arrays, sort-dedup table, scalar slot 0) settles into it, so
@@ -112,8 +113,9 @@ k_post_sortkey(const uint32_t* __restrict__ flags,
 /* canonical MutTableKey order of the blob's groups as a device permutation
  * (the comparator of bkgpu_agg_fetch: flags first, then each non-NULL key's
  * encoding in key order): stable LSD radix passes from the last key to the
- * first, then the flag byte. Returns a pool buffer (caller frees) or null. */
-static uint32_t* post_canonical_perm(const BkgAggOut* o, double* t_ms) {
+ * first, then the flag byte (pass p sorts key n_group - 1 - p; key -1 is the
+ * flag byte). Returns the permutation, owned by bufs, or null. */
+static uint32_t* post_canonical_perm(const BkgAggOut* o, PoolBufs& bufs) {
     const BkQuerySpec& q = o->q;
     const int64_t n = o->ngroups, c = o->blob_groups;
     const uint8_t* b = o->blob;
@@ -121,47 +123,21 @@ static uint32_t* post_canonical_perm(const BkgAggOut* o, double* t_ms) {
     const uint64_t* kw[2] = {(const uint64_t*)(b + c * 4),
                              (const uint64_t*)(b + c * 12)};
     const BkKeyLayout kl = bk_key_layout(&q);
-    uint32_t *pa = nullptr, *pb = nullptr;
-    uint64_t *keys = nullptr, *keys_out = nullptr;
-    void* rp_tmp = nullptr;
-    size_t rp_bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, rp_bytes, (uint64_t*)nullptr,
-                                    (uint64_t*)nullptr, (uint32_t*)nullptr,
-                                    (uint32_t*)nullptr, (size_t)n, 0, 64);
-    bool ok = pool_alloc((void**)&pa, (size_t)n * 4) == hipSuccess &&
-              pool_alloc((void**)&pb, (size_t)n * 4) == hipSuccess &&
-              pool_alloc((void**)&keys, (size_t)n * 8) == hipSuccess &&
-              pool_alloc((void**)&keys_out, (size_t)n * 8) == hipSuccess &&
-              pool_alloc(&rp_tmp, rp_bytes ? rp_bytes : 1) == hipSuccess;
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    bool first = true;
-    double t0 = t_ms ? now_ms() : 0;
-    for (int k = q.n_group - 1; ok && k >= -1; k--) {
-        const bool fl = k < 0;
-        const int bits = fl ? 8 : kl.bits[k];
-        hipLaunchKernelGGL(k_post_sortkey, dim3(blocks), dim3(256), 0, 0,
-                           flags, fl ? kw[0] : kw[kl.word[k]],
-                           first ? (const uint32_t*)nullptr : pa, n,
-                           fl ? 0 : kl.shift[k], bk_key_mask(bits),
-                           fl ? -1 : 7 - k, keys);
-        if (first)
-            hipLaunchKernelGGL(k_iota, dim3(256), dim3(256), 0, 0, pa,
-                               (uint64_t)n);
-        ok = hipGetLastError() == hipSuccess &&
-             rocprim::radix_sort_pairs(rp_tmp, rp_bytes, keys, keys_out, pa,
-                                       pb, (size_t)n, 0, (unsigned)bits)
-                 == hipSuccess;
-        std::swap(pa, pb);
-        first = false;
-    }
-    if (ok && t_ms) { (void)hipDeviceSynchronize(); *t_ms = now_ms() - t0; }
-    pool_free(pb); pool_free(keys); pool_free(keys_out); pool_free(rp_tmp);
-    if (!ok) {
-        set_err("agg_to_table: canonical sort failed");
-        pool_free(pa);
-        return nullptr;
-    }
-    return pa;
+    auto bits_of = [&](int pass) {
+        const int k = q.n_group - 1 - pass;
+        return k < 0 ? 8 : (int)kl.bits[k];
+    };
+    return dev_lsd_perm_sort(
+        bufs, (uint64_t)n, q.n_group + 1, bits_of,
+        [&](int pass, const uint32_t* perm, uint64_t* keys) {
+            const int k = q.n_group - 1 - pass;
+            const bool fl = k < 0;
+            hipLaunchKernelGGL(k_post_sortkey, dim3(blocks), dim3(256), 0, 0,
+                               flags, fl ? kw[0] : kw[kl.word[k]], perm, n,
+                               fl ? 0 : kl.shift[k], bk_key_mask(bits_of(pass)),
+                               fl ? -1 : 7 - k, keys);
+        }, 256);
 }
 
 extern "C" BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src,
@@ -205,31 +181,29 @@ extern "C" BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src,
         src_col[col] = ((at == BK_AGG_MIN || at == BK_AGG_MAX) &&
                         q.aggs[a].prog_len == 0) ? q.aggs[a].col : -1;
     }
+    PoolBufs bufs;
     uint32_t* d_mask = nullptr;
     uint32_t* perm = nullptr;
     uint32_t h_mask = 0;
     double ms_sort = 0, ms_fin = 0;
     bool ok = true;
     for (int col = 0; ok && col < t->ncols; col++) {
-        const size_t es = elem_size(t->specs[col].col_type);
-        if (es == 0) { set_err("agg_to_table: unsupported column type"); ok = false; break; }
-        t->width[col] = (uint8_t)es;
-        /* every table column carries the 16-byte tail pad (cell_i64) */
-        ok = hipMalloc(&t->data[col], (size_t)n * es + 16) == hipSuccess;
         const bool count_shaped = col >= q.n_group &&
             bk_agg_count_shaped(pt.agg_type[col - q.n_group]);
-        if (ok && !count_shaped && n > 0)
-            ok = hipMalloc((void**)&t->valid[col], (size_t)n) == hipSuccess;
-        if (!ok) set_err("agg_to_table: hipMalloc column failed");
+        ok = table_alloc_col(t, col, t->specs[col].col_type, n,
+                             !count_shaped && n > 0) == hipSuccess;
+        if (!ok) set_err("agg_to_table: column allocation failed");
         pc.data[slot_of[col]] = t->data[col];
         pc.valid[slot_of[col]] = t->valid[col];
     }
     if (ok && n > 0) {
         if (canonical && q.n_group > 0 && n > 1) {
-            perm = post_canonical_perm(o, timing ? &ms_sort : nullptr);
+            double t0 = timing ? now_ms() : 0;
+            perm = post_canonical_perm(o, bufs);
             ok = perm != nullptr;
+            if (ok && timing) { (void)hipDeviceSynchronize(); ms_sort = now_ms() - t0; }
         }
-        ok = ok && pool_alloc((void**)&d_mask, 4) == hipSuccess &&
+        ok = ok && bufs.get(&d_mask, 4) == hipSuccess &&
              hipMemset(d_mask, 0, 4) == hipSuccess;
         if (ok) {
             const uint8_t* b = o->blob;
@@ -247,23 +221,10 @@ extern "C" BkgTable* bkgpu_agg_to_table(BkgAggOut* o, const BkgTable* dict_src,
             if (timing) ms_fin = now_ms() - t0;
         }
     }
-    pool_free(d_mask);
-    pool_free(perm);
     if (!ok) { bkgpu_table_free(t); return nullptr; }
-    for (int col = 0; col < t->ncols; col++) {
-        /* keep validity only where a NULL was seen: a NULL-free result stays
-         * eligible for the SIMPLE / dense / sort-dedup routes downstream */
-        if ((h_mask >> slot_of[col]) & 1) {
-            t->specs[col].null_frac_x1e6 = 1;
-        } else if (t->valid[col]) {
-            (void)hipFree(t->valid[col]);
-            t->valid[col] = nullptr;
-        }
-        const int sc = src_col[col];
-        if (t->specs[col].col_type == BK_STRING && dict_src && sc >= 0 &&
-            sc < dict_src->ncols && dict_src->dict[sc])
-            t->dict[col] = new std::vector<std::string>(*dict_src->dict[sc]);
-    }
+    for (int col = 0; col < t->ncols; col++)
+        table_trim_validity(t, col, (h_mask >> slot_of[col]) & 1, dict_src,
+                            src_col[col]);
     if (timing)
         fprintf(stderr, "[bkgpu] agg_to_table: %lld groups, perm sort %.3f ms, "
                         "finalize %.3f ms\n", (long long)n, ms_sort, ms_fin);

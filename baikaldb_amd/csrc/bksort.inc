@@ -27,8 +27,6 @@
 // nullable FIRST order column makes word 0 a marker, which falls back to
 // the scalar per-row load path in the scans.
 
-#include <rocprim/rocprim.hpp>
-
 #define TOPK_MAX_ORDER 4
 #define TOPK_MAX_WORDS (2 * TOPK_MAX_ORDER + 1)
 
@@ -442,44 +440,32 @@ __global__ void k_topk_permute(const uint64_t* in, uint64_t cap_in,
             out[(size_t)w * cap_out + i] = in[(size_t)w * cap_in + idx[i]];
 }
 
-__global__ void k_iota(uint32_t* v, uint64_t n) {
-    uint64_t gstride = (uint64_t)gridDim.x * blockDim.x;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
-         i += gstride)
-        v[i] = (uint32_t)i;
-}
-
 static float g_topk_ms = 0.f;
 extern "C" double bkgpu_topk_kernel_ms(void) { return g_topk_ms; }
 
 /* stable LSD sort of `n` entries (SoA word planes, capacity cap) by the
  * composite (word 0 most significant). Ping-pongs between buf and tmp;
- * returns pointer holding the sorted data (== buf or tmp). */
+ * returns pointer holding the sorted data (== buf or tmp), or nullptr with
+ * g_err set. */
 static uint64_t* topk_lsd_sort(uint64_t* buf, uint64_t* tmp, uint64_t cap,
                                uint64_t n, int W) {
     if (n <= 1) return buf;
+    PoolBufs bufs;
     uint32_t *idx_in = nullptr, *idx_out = nullptr;
     uint64_t* keys_out = nullptr;
-    void* rp_tmp = nullptr;
-    size_t rp_bytes = 0;
-    (void)rocprim::radix_sort_pairs(nullptr, rp_bytes, (uint64_t*)nullptr,
-                                    (uint64_t*)nullptr, (uint32_t*)nullptr,
-                                    (uint32_t*)nullptr, n);
-    if (pool_alloc((void**)&idx_in, n * 4) != hipSuccess) return nullptr;
-    if (pool_alloc((void**)&idx_out, n * 4) != hipSuccess) return nullptr;
-    if (pool_alloc((void**)&keys_out, n * 8) != hipSuccess) return nullptr;
-    if (pool_alloc(&rp_tmp, rp_bytes ? rp_bytes : 1) != hipSuccess) return nullptr;
+    BK_TRY("topk sort", bufs.get(&idx_in, n * 4), nullptr);
+    BK_TRY("topk sort", bufs.get(&idx_out, n * 4), nullptr);
+    BK_TRY("topk sort", bufs.get(&keys_out, n * 8), nullptr);
     uint64_t* cur = buf;
     uint64_t* oth = tmp;
     for (int w = W - 1; w >= 0; w--) {  /* least significant word first */
-        hipLaunchKernelGGL(k_iota, dim3(256), dim3(256), 0, 0, idx_in, n);
-        (void)rocprim::radix_sort_pairs(rp_tmp, rp_bytes, cur + (size_t)w * cap,
-                                        keys_out, idx_in, idx_out, n);
+        dev_iota(idx_in, n, 256);
+        BK_TRY("topk sort", dev_sort_pairs(bufs, cur + (size_t)w * cap, keys_out,
+                                           idx_in, idx_out, n, 0, 64), nullptr);
         hipLaunchKernelGGL(k_topk_permute, dim3(256), dim3(256), 0, 0,
                            cur, cap, idx_out, n, W, oth, cap);
         std::swap(cur, oth);
     }
-    pool_free(idx_in); pool_free(idx_out); pool_free(keys_out); pool_free(rp_tmp);
     return cur;
 }
 
@@ -572,36 +558,32 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
              *candA = nullptr, *candB = nullptr,
              *outbufA = nullptr, *outbufB = nullptr;
     uint32_t* err = nullptr;
-    int rc = -1;
     uint64_t h_host[8 * 256];
     Pref8 pref{};
     uint64_t* prefd = nullptr;   /* device copy for the >8-byte cmp path */
     int nbytes = 0;
     int64_t need = limit;
     uint64_t n_cand = 0;
-    uint64_t* res = nullptr;
     uint64_t n_below = 0, n_out = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    int64_t got = -1;
+    PoolBufs bufs;
+    DevEvents<2> evs;
+    hipEvent_t &ev0 = evs.e[0], &ev1 = evs.e[1];
 
-    #define TCHECK(x) do { if ((x) != hipSuccess) { \
-        snprintf(g_err, sizeof g_err, "topk %s:%d %s", __FILE__, __LINE__, \
-                 hipGetErrorString(hipGetLastError())); goto done; } } while (0)
-    TCHECK(pool_alloc((void**)&histo, 8 * 256 * 8));
-    TCHECK(pool_alloc((void**)&prefd, sizeof(Pref8)));
-    TCHECK(hipMemcpy(prefd, pref.w, sizeof(Pref8), hipMemcpyHostToDevice));
-    TCHECK(pool_alloc((void**)&ctr, 8));
-    TCHECK(pool_alloc((void**)&ctr2, 8));
-    TCHECK(hipMemset(ctr2, 0, 8));
-    TCHECK(pool_alloc((void**)&err, 4));
-    TCHECK(pool_alloc((void**)&candA, cand_cap * W * 8));
-    TCHECK(pool_alloc((void**)&candB, cand_cap * W * 8));
-    TCHECK(pool_alloc((void**)&outbufA, out_cap * W * 8));
-    TCHECK(pool_alloc((void**)&outbufB, out_cap * W * 8));
-    TCHECK(hipMemset(err, 0, 4));
-    TCHECK(hipEventCreate(&ev0));
-    TCHECK(hipEventCreate(&ev1));
-    TCHECK(hipEventRecord(ev0));
+    BK_TRY("topk", bufs.get(&histo, 8 * 256 * 8), -1);
+    BK_TRY("topk", bufs.get(&prefd, sizeof(Pref8)), -1);
+    BK_TRY("topk", hipMemcpy(prefd, pref.w, sizeof(Pref8), hipMemcpyHostToDevice),
+           -1);
+    BK_TRY("topk", bufs.get(&ctr, 8), -1);
+    BK_TRY("topk", bufs.get(&ctr2, 8), -1);
+    BK_TRY("topk", hipMemset(ctr2, 0, 8), -1);
+    BK_TRY("topk", bufs.get(&err, 4), -1);
+    BK_TRY("topk", bufs.get(&candA, cand_cap * W * 8), -1);
+    BK_TRY("topk", bufs.get(&candB, cand_cap * W * 8), -1);
+    BK_TRY("topk", bufs.get(&outbufA, out_cap * W * 8), -1);
+    BK_TRY("topk", bufs.get(&outbufB, out_cap * W * 8), -1);
+    BK_TRY("topk", hipMemset(err, 0, 4), -1);
+    BK_TRY("topk", evs.create(), -1);
+    BK_TRY("topk", hipEventRecord(ev0), -1);
 
     /* ---- phase 1: streaming refinement until the == prefix set fits the
      * candidate buffer. Each scan histograms all 8 bytes of the current
@@ -610,7 +592,7 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
         bool collected = false;
         int64_t total = -1;   /* rows matching current prefix (unknown yet) */
         while (!collected) {
-            TCHECK(hipMemset(histo, 0, 8 * 256 * 8));
+            BK_TRY("topk", hipMemset(histo, 0, 8 * 256 * 8), -1);
             hipLaunchKernelGGL(scan8, dim3(2048), dim3(256),
                                8 * 256 * 4 + 24, 0,
                                dc, *qk, tdc, ts, row_begin, row_end, pref.w[0],
@@ -619,8 +601,8 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
                                (uint64_t*)nullptr, err, 0,
                                (uint64_t*)nullptr, 0, (uint64_t*)nullptr,
                                1024);
-            TCHECK(hipGetLastError());
-            TCHECK(hipMemcpy(h_host, histo, 8 * 256 * 8, hipMemcpyDeviceToHost));
+            BK_TRY("topk", hipGetLastError(), -1);
+            BK_TRY("topk", hipMemcpy(h_host, histo, 8 * 256 * 8, hipMemcpyDeviceToHost), -1);
             int word0 = nbytes / 8;
             for (int b = nbytes % 8; b < 8; b++) {
                 const uint64_t* h = h_host + (size_t)b * 256;
@@ -644,16 +626,16 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
                 need -= (int64_t)cum;
                 pref.w[nbytes / 8] |= ((uint64_t)pick) << (8 * (7 - nbytes % 8));
                 nbytes++;
-                TCHECK(hipMemcpy(prefd, pref.w, sizeof(Pref8),
-                                 hipMemcpyHostToDevice));
+                BK_TRY("topk", hipMemcpy(prefd, pref.w, sizeof(Pref8),
+                                         hipMemcpyHostToDevice), -1);
                 int64_t cnt = (int64_t)h[pick];
                 if ((uint64_t)cnt <= cand_cap) {
-                    TCHECK(hipMemset(ctr, 0, 8));
+                    BK_TRY("topk", hipMemset(ctr, 0, 8), -1);
                     if (fuse) {
                         /* fused: == candidates AND the strictly-below set
                          * in ONE scan (ctr2 keeps accumulating through the
                          * phase-2 refinement's below-appends) */
-                        TCHECK(hipMemset(ctr2, 0, 8));
+                        BK_TRY("topk", hipMemset(ctr2, 0, 8), -1);
                         hipLaunchKernelGGL(
                             fuse_tk8 ? scan8 : scan4, dim3(2048), dim3(256),
                             (size_t)fuse_cap * W * 8 * 2 + 24, 0,
@@ -676,11 +658,11 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
                                            (uint64_t*)nullptr, 0,
                                            (uint64_t*)nullptr, 1024);
                     }
-                    TCHECK(hipGetLastError());
-                    TCHECK(hipMemcpy(&n_cand, ctr, 8, hipMemcpyDeviceToHost));
+                    BK_TRY("topk", hipGetLastError(), -1);
+                    BK_TRY("topk", hipMemcpy(&n_cand, ctr, 8, hipMemcpyDeviceToHost), -1);
                     uint32_t e_host = 0;
-                    TCHECK(hipMemcpy(&e_host, err, 4, hipMemcpyDeviceToHost));
-                    if (e_host) { set_err("sort_topk: candidate overflow"); goto done; }
+                    BK_TRY("topk", hipMemcpy(&e_host, err, 4, hipMemcpyDeviceToHost), -1);
+                    if (e_host) { set_err("sort_topk: candidate overflow"); return -1; }
                     collected = true;
                     break;
                 }
@@ -695,11 +677,11 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
     /* ---- phase 2: candidate-array refinement ---- */
     while (n_cand > (uint64_t)std::max<int64_t>(need, 1) &&
            (int64_t)n_cand > (int64_t)out_cap / 2 && nbytes < 8 * W) {
-        TCHECK(hipMemset(histo, 0, 256 * 8));
+        BK_TRY("topk", hipMemset(histo, 0, 256 * 8), -1);
         hipLaunchKernelGGL(k_topk_histo_cand, dim3(512), dim3(256), 0, 0,
                            candA, cand_cap, n_cand, nbytes, histo);
-        TCHECK(hipGetLastError());
-        TCHECK(hipMemcpy(h_host, histo, 256 * 8, hipMemcpyDeviceToHost));
+        BK_TRY("topk", hipGetLastError(), -1);
+        BK_TRY("topk", hipMemcpy(h_host, histo, 256 * 8, hipMemcpyDeviceToHost), -1);
         uint64_t cum = 0;
         int pick = 255;
         for (int bkt = 0; bkt < 256; bkt++) {
@@ -709,24 +691,24 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
         need -= (int64_t)cum;
         pref.w[nbytes / 8] |= ((uint64_t)pick) << (8 * (7 - nbytes % 8));
         nbytes++;
-        TCHECK(hipMemcpy(prefd, pref.w, sizeof(Pref8),
-                         hipMemcpyHostToDevice));
-        TCHECK(hipMemset(ctr, 0, 8));
+        BK_TRY("topk", hipMemcpy(prefd, pref.w, sizeof(Pref8),
+                                 hipMemcpyHostToDevice), -1);
+        BK_TRY("topk", hipMemset(ctr, 0, 8), -1);
         hipLaunchKernelGGL(k_topk_filter_cand, dim3(512), dim3(256), 0, 0,
                            candA, cand_cap, n_cand, nbytes - 1, (uint32_t)pick,
                            W, candB, cand_cap, ctr,
                            fuse ? outbufA : (uint64_t*)nullptr, out_cap,
                            fuse ? ctr2 : (uint64_t*)nullptr);
-        TCHECK(hipGetLastError());
-        TCHECK(hipMemcpy(&n_cand, ctr, 8, hipMemcpyDeviceToHost));
+        BK_TRY("topk", hipGetLastError(), -1);
+        BK_TRY("topk", hipMemcpy(&n_cand, ctr, 8, hipMemcpyDeviceToHost), -1);
         std::swap(candA, candB);
     }
 
     /* ---- sort candidates, keep the `need` smallest ---- */
     {
         uint64_t* sorted = topk_lsd_sort(candA, candB, cand_cap, n_cand, W);
-        if (!sorted && n_cand > 1) { set_err("topk sort alloc failed"); goto done; }
-        if (sorted && sorted != candA) std::swap(candA, candB);
+        if (!sorted) return -1;
+        if (sorted != candA) std::swap(candA, candB);
         /* candA now holds sorted candidates */
     }
     if ((uint64_t)need > n_cand) need = (int64_t)n_cand;
@@ -734,9 +716,9 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
     /* ---- the strictly-below set: already collected by the fused scan
      * (+ the refinement's below-appends); two-pass flow rescans ---- */
     if (fuse) {
-        TCHECK(hipMemcpy(&n_below, ctr2, 8, hipMemcpyDeviceToHost));
+        BK_TRY("topk", hipMemcpy(&n_below, ctr2, 8, hipMemcpyDeviceToHost), -1);
     } else {
-        TCHECK(hipMemset(ctr, 0, 8));
+        BK_TRY("topk", hipMemset(ctr, 0, 8), -1);
         hipLaunchKernelGGL(scan4, dim3(2048), dim3(256),
                            (size_t)stage_cap * W * 8 + 24, 0,
                            dc, *qk, tdc, ts, row_begin, row_end, pref.w[0],
@@ -744,44 +726,34 @@ extern "C" int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
                            TOPK_COLLECT_LT, (uint64_t*)nullptr, outbufA,
                            out_cap, ctr, err, stage_cap,
                            (uint64_t*)nullptr, 0, (uint64_t*)nullptr, 1024);
-        TCHECK(hipGetLastError());
-        TCHECK(hipMemcpy(&n_below, ctr, 8, hipMemcpyDeviceToHost));
+        BK_TRY("topk", hipGetLastError(), -1);
+        BK_TRY("topk", hipMemcpy(&n_below, ctr, 8, hipMemcpyDeviceToHost), -1);
     }
     {
         uint32_t e_host = 0;
-        TCHECK(hipMemcpy(&e_host, err, 4, hipMemcpyDeviceToHost));
+        BK_TRY("topk", hipMemcpy(&e_host, err, 4, hipMemcpyDeviceToHost), -1);
         if (e_host || n_below > out_cap) {
             set_err("sort_topk: below-set overflow (internal)");
-            goto done;
+            return -1;
         }
     }
     /* append the needed candidates behind the below set */
     for (int w = 0; w < W; w++) {
-        TCHECK(hipMemcpy(outbufA + (size_t)w * out_cap + n_below,
-                         candA + (size_t)w * cand_cap,
-                         (size_t)need * 8, hipMemcpyDeviceToDevice));
+        BK_TRY("topk", hipMemcpy(outbufA + (size_t)w * out_cap + n_below,
+                                 candA + (size_t)w * cand_cap, (size_t)need * 8,
+                                 hipMemcpyDeviceToDevice), -1);
     }
     n_out = n_below + (uint64_t)need;
     if (n_out > (uint64_t)limit) n_out = (uint64_t)limit;
 
     /* ---- final full sort of the <= limit survivors ---- */
-    res = topk_lsd_sort(outbufA, outbufB, out_cap, n_out, W);
-    if (!res && n_out > 1) { set_err("topk final sort alloc failed"); goto done; }
-    if (!res) res = outbufA;
-    TCHECK(hipEventRecord(ev1));
-    TCHECK(hipEventSynchronize(ev1));
-    TCHECK(hipEventElapsedTime(&g_topk_ms, ev0, ev1));
+    uint64_t* res = topk_lsd_sort(outbufA, outbufB, out_cap, n_out, W);
+    if (!res) return -1;
+    BK_TRY("topk", hipEventRecord(ev1), -1);
+    BK_TRY("topk", hipEventSynchronize(ev1), -1);
+    BK_TRY("topk", hipEventElapsedTime(&g_topk_ms, ev0, ev1), -1);
     /* rowids are the last word plane */
-    TCHECK(hipMemcpy(out_rows, res + (size_t)(W - 1) * out_cap,
-                     (size_t)n_out * 8, hipMemcpyDeviceToHost));
-    got = (int64_t)n_out;
-    rc = 0;
-done:
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    pool_free(histo); pool_free(ctr); pool_free(ctr2); pool_free(err);
-    pool_free(prefd);
-    pool_free(candA); pool_free(candB); pool_free(outbufA); pool_free(outbufB);
-    #undef TCHECK
-    return rc == 0 ? got : -1;
+    BK_TRY("topk", hipMemcpy(out_rows, res + (size_t)(W - 1) * out_cap,
+                             (size_t)n_out * 8, hipMemcpyDeviceToHost), -1);
+    return (int64_t)n_out;
 }

@@ -624,31 +624,21 @@ extern "C" int64_t bkgpu_window_multi(BkgTable* t, const BkQuerySpec* q,
     int st_levels = 0;
     int64_t* bounds = nullptr;
     BkWindowFn* dfns = nullptr;
-    void* tmp = nullptr;
     int64_t* d_out_i = nullptr;
     double* d_out_d = nullptr;
     uint8_t* d_out_null = nullptr;
-    auto cleanup = [&]() {
-        pool_free(rowid); pool_free(segf); pool_free(peerf); pool_free(partid1);
-        pool_free(peerB); pool_free(peerC); pool_free(states); pool_free(bounds);
-        pool_free(peer_end); pool_free(FS); pool_free(FC);
-        pool_free(ST); pool_free(ENCo);
-        pool_free(dfns); pool_free(tmp); pool_free(d_out_i); pool_free(d_out_d);
-        pool_free(d_out_null);
-    };
-    #define WCHECK(x) do { if ((x) != hipSuccess) { \
-        snprintf(g_err, sizeof g_err, "window %s:%d %s", __FILE__, __LINE__, \
-                 hipGetErrorString(hipGetLastError())); cleanup(); return -1; } } while (0)
-    WCHECK(pool_alloc((void**)&rowid, (size_t)n * 8));
-    WCHECK(hipMemcpy(rowid, out_rowids, (size_t)n * 8, hipMemcpyHostToDevice));
-    WCHECK(pool_alloc((void**)&segf, (size_t)n * 4));
-    WCHECK(pool_alloc((void**)&peerf, (size_t)n * 4));
-    WCHECK(pool_alloc((void**)&partid1, (size_t)n * 4));
-    WCHECK(pool_alloc((void**)&peerB, (size_t)n * 8));
-    WCHECK(pool_alloc((void**)&peerC, (size_t)n * 8));
-    WCHECK(pool_alloc((void**)&dfns, sizeof(BkWindowFn) * (size_t)nfns));
-    WCHECK(hipMemcpy(dfns, fns, sizeof(BkWindowFn) * (size_t)nfns,
-                     hipMemcpyHostToDevice));
+    PoolBufs bufs;
+    BK_TRY("window", bufs.get(&rowid, (size_t)n * 8), -1);
+    BK_TRY("window", hipMemcpy(rowid, out_rowids, (size_t)n * 8,
+                               hipMemcpyHostToDevice), -1);
+    BK_TRY("window", bufs.get(&segf, (size_t)n * 4), -1);
+    BK_TRY("window", bufs.get(&peerf, (size_t)n * 4), -1);
+    BK_TRY("window", bufs.get(&partid1, (size_t)n * 4), -1);
+    BK_TRY("window", bufs.get(&peerB, (size_t)n * 8), -1);
+    BK_TRY("window", bufs.get(&peerC, (size_t)n * 8), -1);
+    BK_TRY("window", bufs.get(&dfns, sizeof(BkWindowFn) * (size_t)nfns), -1);
+    BK_TRY("window", hipMemcpy(dfns, fns, sizeof(BkWindowFn) * (size_t)nfns,
+                               hipMemcpyHostToDevice), -1);
 
     DevCols dc = table_cols(t);
     WinCompareCols w{};
@@ -660,33 +650,22 @@ extern "C" int64_t bkgpu_window_multi(BkgTable* t, const BkQuerySpec* q,
     hipLaunchKernelGGL(k_win_flags, dim3(blocks), dim3(threads), 0, 0,
                        dc, w, rowid, n, segf, peerf);
     /* partition ids (1-based): inclusive sum scan of segf */
-    size_t tb = 0;
-    (void)rocprim::inclusive_scan(nullptr, tb, segf, partid1, (size_t)n,
-                                  rocprim::plus<uint32_t>());
-    size_t tb2 = 0;
-    (void)rocprim::inclusive_scan(nullptr, tb2, peerf, peerC, (size_t)n,
-                                  rocprim::plus<uint64_t>());
-    size_t tb3 = 0;
-    (void)rocprim::inclusive_scan(nullptr, tb3, peerB, peerB, (size_t)n,
-                                  rocprim::maximum<uint64_t>());
-    size_t tmax = std::max(tb, std::max(tb2, tb3));
-    WCHECK(pool_alloc(&tmp, tmax ? tmax : 8));
-    WCHECK(rocprim::inclusive_scan(tmp, tb, segf, partid1, (size_t)n,
-                                   rocprim::plus<uint32_t>()));
-    WCHECK(rocprim::inclusive_scan(tmp, tb2, peerf, peerC, (size_t)n,
-                                   rocprim::plus<uint64_t>()));
+    BK_TRY("window", dev_inclusive_scan(bufs, segf, partid1, (size_t)n,
+                                        DevPlus<uint32_t>()), -1);
+    BK_TRY("window", dev_inclusive_scan(bufs, peerf, peerC, (size_t)n,
+                                        DevPlus<uint64_t>()), -1);
     hipLaunchKernelGGL(k_win_peerpos, dim3(blocks), dim3(threads), 0, 0,
                        partid1, peerf, n, peerB);
-    WCHECK(rocprim::inclusive_scan(tmp, tb3, peerB, peerB, (size_t)n,
-                                   rocprim::maximum<uint64_t>()));
+    BK_TRY("window", dev_inclusive_scan(bufs, peerB, peerB, (size_t)n,
+                                        DevMax<uint64_t>()), -1);
     uint32_t np = 0;
-    WCHECK(hipMemcpy(&np, partid1 + (n - 1), 4, hipMemcpyDeviceToHost));
-    if (np >= (1u << 24)) { set_err("window: too many partitions"); cleanup(); return -1; }
-    WCHECK(pool_alloc((void**)&bounds, ((size_t)np + 1) * 8));
+    BK_TRY("window", hipMemcpy(&np, partid1 + (n - 1), 4, hipMemcpyDeviceToHost), -1);
+    if (np >= (1u << 24)) { set_err("window: too many partitions"); return -1; }
+    BK_TRY("window", bufs.get(&bounds, ((size_t)np + 1) * 8), -1);
     hipLaunchKernelGGL(k_win_bounds, dim3(blocks), dim3(threads), 0, 0,
                        partid1, segf, n, bounds, (int64_t)np);
-    WCHECK(pool_alloc((void**)&states, (size_t)np * nfns * 2 * 8));
-    WCHECK(hipMemset(states, 0, (size_t)np * nfns * 2 * 8));
+    BK_TRY("window", bufs.get(&states, (size_t)np * nfns * 2 * 8), -1);
+    BK_TRY("window", hipMemset(states, 0, (size_t)np * nfns * 2 * 8), -1);
     bool any_agg = false;
     for (int f = 0; f < nfns; f++) any_agg |= fns[f].fn_type <= BK_WIN_MAX;
     if (any_agg) {
@@ -697,14 +676,15 @@ extern "C" int64_t bkgpu_window_multi(BkgTable* t, const BkQuerySpec* q,
                            states, dfns, nfns);
     }
     uint64_t total_peers = 0;
-    WCHECK(hipMemcpy(&total_peers, peerC + (n - 1), 8, hipMemcpyDeviceToHost));
-    WCHECK(pool_alloc((void**)&peer_end, (total_peers + 1) * 8));
-    WCHECK(hipMemset(peer_end, 0, (total_peers + 1) * 8));
+    BK_TRY("window", hipMemcpy(&total_peers, peerC + (n - 1), 8,
+                               hipMemcpyDeviceToHost), -1);
+    BK_TRY("window", bufs.get(&peer_end, (total_peers + 1) * 8), -1);
+    BK_TRY("window", hipMemset(peer_end, 0, (total_peers + 1) * 8), -1);
     hipLaunchKernelGGL(k_win_peerend, dim3(blocks), dim3(threads), 0, 0,
                        peerC, n, peer_end);
     if (frame_rows) {
-        WCHECK(pool_alloc((void**)&FS, (size_t)nfns * n * 8));
-        WCHECK(pool_alloc((void**)&FC, (size_t)nfns * n * 8));
+        BK_TRY("window", bufs.get(&FS, (size_t)nfns * n * 8), -1);
+        BK_TRY("window", bufs.get(&FC, (size_t)nfns * n * 8), -1);
         hipLaunchKernelGGL(k_win_frame_vals, dim3(blocks), dim3(threads), 0, 0,
                            dc, rowid, dfns, nfns, n, FS, FC);
         for (int f = 0; f < nfns; f++) {
@@ -712,31 +692,20 @@ extern "C" int64_t bkgpu_window_multi(BkgTable* t, const BkQuerySpec* q,
             if (ft > BK_WIN_MAX) continue;
             uint64_t* Sf = FS + (size_t)f * n;
             uint64_t* Cf = FC + (size_t)f * n;
-            size_t tc = 0;
-            (void)rocprim::inclusive_scan(nullptr, tc, Cf, Cf, (size_t)n,
-                                          rocprim::plus<uint64_t>());
-            if (tc > tmax) {
-                pool_free(tmp);
-                tmp = nullptr;
-                WCHECK(pool_alloc(&tmp, tc));
-                tmax = tc;
-            }
-            WCHECK(rocprim::inclusive_scan(tmp, tc, Cf, Cf, (size_t)n,
-                                           rocprim::plus<uint64_t>()));
+            BK_TRY("window", dev_inclusive_scan(bufs, Cf, Cf, (size_t)n,
+                                                DevPlus<uint64_t>()), -1);
             if (ft == BK_WIN_MIN || ft == BK_WIN_MAX || ft == BK_WIN_COUNT ||
                 ft == BK_WIN_COUNT_STAR)
                 continue;   /* counts only */
             bool dbl = fns[f].fn_type == BK_WIN_AVG ||
                        (fns[f].col >= 0 &&
                         t->specs[fns[f].col].col_type == BK_DOUBLE);
-            if (dbl) {
-                WCHECK(rocprim::inclusive_scan(tmp, tc, (double*)Sf,
-                                               (double*)Sf, (size_t)n,
-                                               rocprim::plus<double>()));
-            } else {
-                WCHECK(rocprim::inclusive_scan(tmp, tc, Sf, Sf, (size_t)n,
-                                               rocprim::plus<uint64_t>()));
-            }
+            if (dbl)
+                BK_TRY("window", dev_inclusive_scan(bufs, (double*)Sf, (double*)Sf,
+                                                    (size_t)n, DevPlus<double>()), -1);
+            else
+                BK_TRY("window", dev_inclusive_scan(bufs, Sf, Sf, (size_t)n,
+                                                    DevPlus<uint64_t>()), -1);
         }
     }
     /* sparse table for frame MIN/MAX: levels sized by the max frame length
@@ -754,10 +723,9 @@ extern "C" int64_t bkgpu_window_multi(BkgTable* t, const BkQuerySpec* q,
         if (st_bytes > (size_t)8 << 30) {
             set_err("window: frame MIN/MAX sparse table would exceed 8 GB "
                     "(bound the frame or reduce rows)");
-            cleanup();
             return -1;
         }
-        WCHECK(pool_alloc((void**)&ST, st_bytes));
+        BK_TRY("window", bufs.get(&ST, st_bytes), -1);
         hipLaunchKernelGGL(k_win_st_base, dim3(blocks), dim3(threads), 0, 0,
                            dc, rowid, dfns, nfns, n, ST);
         for (int k = 1; k < st_levels; k++) {
@@ -770,24 +738,25 @@ extern "C" int64_t bkgpu_window_multi(BkgTable* t, const BkQuerySpec* q,
     int ord_col = norder >= 1 ? order[0].col : -1;
     int ord_nf = norder >= 1 ? order[0].is_null_first : 1;
     if (frame_rows == 4) {
-        WCHECK(pool_alloc((void**)&ENCo, (size_t)n * 8));
+        BK_TRY("window", bufs.get(&ENCo, (size_t)n * 8), -1);
         hipLaunchKernelGGL(k_win_ordenc, dim3(blocks), dim3(threads), 0, 0,
                            dc, ord_col, rowid, n, ENCo);
     }
-    WCHECK(pool_alloc((void**)&d_out_i, (size_t)nfns * n * 8));
-    WCHECK(pool_alloc((void**)&d_out_d, (size_t)nfns * n * 8));
-    WCHECK(pool_alloc((void**)&d_out_null, (size_t)nfns * n));
+    BK_TRY("window", bufs.get(&d_out_i, (size_t)nfns * n * 8), -1);
+    BK_TRY("window", bufs.get(&d_out_d, (size_t)nfns * n * 8), -1);
+    BK_TRY("window", bufs.get(&d_out_null, (size_t)nfns * n), -1);
     hipLaunchKernelGGL(k_win_emit, dim3(blocks), dim3(threads), 0, 0,
                        dc, rowid, partid1, peerB, peerC, peer_end, bounds,
                        states, dfns, nfns, n, frame_rows, f_pre, f_fol,
                        FS, FC, ST, st_levels, ENCo, ord_col, ord_nf,
                        d_out_i, d_out_d, d_out_null);
-    WCHECK(hipGetLastError());
-    WCHECK(hipMemcpy(out_i, d_out_i, (size_t)nfns * n * 8, hipMemcpyDeviceToHost));
-    WCHECK(hipMemcpy(out_d, d_out_d, (size_t)nfns * n * 8, hipMemcpyDeviceToHost));
-    WCHECK(hipMemcpy(out_null, d_out_null, (size_t)nfns * n, hipMemcpyDeviceToHost));
-    cleanup();
-    #undef WCHECK
+    BK_TRY("window", hipGetLastError(), -1);
+    BK_TRY("window", hipMemcpy(out_i, d_out_i, (size_t)nfns * n * 8,
+                               hipMemcpyDeviceToHost), -1);
+    BK_TRY("window", hipMemcpy(out_d, d_out_d, (size_t)nfns * n * 8,
+                               hipMemcpyDeviceToHost), -1);
+    BK_TRY("window", hipMemcpy(out_null, d_out_null, (size_t)nfns * n,
+                               hipMemcpyDeviceToHost), -1);
     return n;
 }
 
