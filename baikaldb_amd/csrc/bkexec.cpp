@@ -8,10 +8,18 @@
 //   RuntimeState counters                   include/runtime/runtime_state.h:237-270
 //   RowBatch / MemRow containers            include/runtime/row_batch.h:24-231,
 //                                           include/mem_row/mem_row.h:28-215
-//   FilterNode::get_next                    src/exec/filter_node.cpp:736-795
+//   ScanNode                                (columnar source; no row mode)
+//   FilterNode::get_next (WHERE / HAVING)   src/exec/filter_node.cpp:736-795
 //   AggNode::open/get_next                  src/exec/agg_node.cpp:405-587
+//   JoinNode (hash equi-join)               src/exec/join_node.cpp, joiner.cpp
 //   SortNode::open/get_next (top-N)         src/exec/sort_node.cpp:278-440
+//   WindowNode                              src/exec/window_node.cpp
 //   LimitNode                               (reached_limit, exec_node.h:186)
+//
+// Shared pieces: HostCols (the gathered-column block every row-emitting node
+// streams from), make_value (one cell -> ExprValue), ExecNode::emit_rows (the
+// one get_next loop), ExecNode::n_slots and source_of (what a blocking node
+// consumes).
 //
 // Like the reference's Acero alternative path (region.cpp:2793-2923), the
 // blocking nodes compile their subtree into ONE engine pipeline at open()
@@ -47,6 +55,19 @@ struct ExprValue {
     double d = 0.0;
     bool is_null() const { return is_null_; }
 };
+
+/* one cell -> ExprValue: a NULL carries no payload, a DOUBLE only d, every
+ * other type only i */
+static inline ExprValue make_value(int32_t type, bool is_null, int64_t i, double d) {
+    ExprValue v;
+    v.type = type;
+    v.is_null_ = is_null;
+    if (!is_null) {
+        if (type == BK_DOUBLE) v.d = d;
+        else v.i = i;
+    }
+    return v;
+}
 
 /* ---- MemRow (mem_row.h:28-215; one tuple, slot-addressed) ---- */
 struct MemRow {
@@ -133,6 +154,8 @@ public:
         return _limit > 0 && _num_rows_returned >= _limit;  /* exec_node.h:186 */
     }
     int32_t node_type() const { return _node_type; }
+    /* slots of a row this node emits as the root (0: emits no rows) */
+    virtual int n_slots() { return 0; }
 
     static ExecNode* create_exec_node(const BkPlanNodeDesc& node);
     /* pre-order flattened plan -> tree (exec_node.cpp create_tree) */
@@ -142,6 +165,29 @@ public:
     int64_t _limit = -1;
     int64_t _num_rows_returned = 0;
 protected:
+    /* The get_next loop of every row-emitting node. Per row, in this order:
+     * cancelled -> reached_limit -> avail() -> batch full -> fill(row). The
+     * source is asked before the batch-full check, so a batch that the last
+     * row filled comes back without eos and only the drained call sets it.
+     * avail(): 1 = a row is ready (refilling the node's chunk if needed),
+     * 0 = drained, < 0 = error (returned as is). fill(row) writes the ready
+     * row and advances the node's cursor. */
+    template <class Avail, class Fill>
+    int emit_rows(RuntimeState* state, RowBatch* batch, bool* eos,
+                  Avail&& avail, Fill&& fill) {
+        while (true) {
+            if (state->is_cancelled()) { *eos = true; return 0; } /* agg_node.cpp:450 */
+            if (reached_limit()) { *eos = true; return 0; }
+            int r = avail();
+            if (r < 0) return r;
+            if (r == 0) { *eos = true; return 0; }
+            if (batch->is_full()) return 0;
+            auto row = std::make_unique<MemRow>(n_slots());
+            fill(row.get());
+            batch->move_row(std::move(row));
+            _num_rows_returned++;
+        }
+    }
     std::vector<ExecNode*> _children;
 private:
     static int build(const BkPlanNodeDesc* nodes, int n, int* pos, ExecNode** out);
@@ -167,6 +213,59 @@ private:
     BkgTable* _table = nullptr;
 };
 
+template <class V>
+static void release(V& v) { V().swap(v); }   /* clear() keeps the capacity */
+
+/* ---- HostCols: the block of gathered columns a row-emitting node streams
+ * from — chosen columns of a device table, fetched for a list of row ids
+ * (bkgpu_gather) and written into MemRow slots one row at a time. ---- */
+class HostCols {
+public:
+    /* n columns of t: cols[0..n), or columns 0..n-1 when cols is null */
+    void bind(BkgTable* t, const int32_t* cols, int n) {
+        _table = t;
+        _src.resize(n);
+        _types.resize(n);
+        _i.resize(n);
+        _d.resize(n);
+        _null.resize(n);
+        for (int c = 0; c < n; c++) {
+            _src[c] = cols ? cols[c] : c;
+            _types[c] = bkgpu_table_col_type(t, _src[c]);
+        }
+    }
+    /* rows rowids[0..n) of every bound column; n == 0 launches nothing */
+    int gather(RuntimeState* state, const int64_t* rowids, int64_t n) {
+        for (size_t c = 0; c < _src.size(); c++) {
+            _i[c].resize(n);
+            _d[c].resize(n);
+            _null[c].resize(n);
+            if (n > 0 &&
+                bkgpu_gather(_table, _src[c], rowids, n, _i[c].data(),
+                             _d[c].data(), _null[c].data()) != 0) {
+                state->error_msg = bkgpu_last_error();
+                return -1;
+            }
+        }
+        return 0;
+    }
+    /* gathered row r -> slots s0 .. s0 + n columns - 1 */
+    void write_row(int64_t r, MemRow* row, int s0) const {
+        const int n = (int)_types.size();
+        for (int c = 0; c < n; c++)
+            row->set_value(s0 + c, make_value(_types[c], _null[c][r] != 0,
+                                              _i[c][r], _d[c][r]));
+    }
+    void clear() { *this = HostCols(); }
+private:
+    BkgTable* _table = nullptr;
+    std::vector<int32_t> _src;     /* table column behind each bound column */
+    std::vector<int32_t> _types;   /* BkType tags */
+    std::vector<std::vector<int64_t>> _i;
+    std::vector<std::vector<double>> _d;
+    std::vector<std::vector<uint8_t>> _null;
+};
+
 /* ---- FilterNode (filter_node.cpp:605-795): holds the conjuncts. When it is
  * an interior node, the blocking parent compiles them into the pipeline;
  * when it is the (effective) root, open() runs the GPU filter and get_next()
@@ -181,6 +280,11 @@ public:
     }
     int n_conjuncts() const { return _n_conjuncts; }
     const BkConjunct* conjuncts() const { return _conjuncts; }
+    /* the one place a FilterNode's conjuncts become a query's filter */
+    void copy_conjuncts(BkQuerySpec* q) const {
+        q->n_conjuncts = _n_conjuncts;
+        memcpy(q->conjuncts, _conjuncts, sizeof(q->conjuncts));
+    }
     bool is_having() const { return _node_type == BK_HAVING_FILTER_NODE; }
     /* As the EFFECTIVE ROOT (SELECT without GROUP BY/ORDER BY) FilterNode
      * emits the passing rows itself (filter_node.cpp:736-795): the GPU
@@ -195,15 +299,15 @@ public:
      * layout and type tags of the AGG root. */
     int open(RuntimeState* state) override;
     int get_next(RuntimeState* state, RowBatch* batch, bool* eos) override;
-    int n_slots();  /* lazily resolved from the scan's table */
+    int n_slots() override;  /* lazily resolved from the scan's table */
     void close(RuntimeState* state) override {
         ExecNode::close(state);
         _opened = false;
         _eos_source = false;
         _scan_pos = 0;
         _src_table = nullptr;
-        _rowids.clear();
-        _cols_i.clear(); _cols_d.clear(); _cols_n.clear();
+        release(_rowids);
+        _cols.clear();
         _iter = 0;
     }
 private:
@@ -220,10 +324,7 @@ private:
     int64_t _nrows = 0;
     int64_t _scan_pos = 0;
     std::vector<int64_t> _rowids;          /* current chunk's survivors */
-    std::vector<std::vector<int64_t>> _cols_i;
-    std::vector<std::vector<double>> _cols_d;
-    std::vector<std::vector<uint8_t>> _cols_n;
-    std::vector<int32_t> _col_types;
+    HostCols _cols;                        /* ... and their cells */
     int64_t _iter = 0;                     /* cursor within the chunk */
 };
 
@@ -238,12 +339,14 @@ static ScanNode* find_scan(ExecNode* n);
  *    then slot indices into [group keys...][agg outputs...];
  *  - a JOIN_NODE makes it the joined table (JoinNode::result_table) under
  *    the WHERE filter passed on the way; columns are then positions in the
- *    join's output list (from_agg is set: the counters stay as the JoinNode
- *    set them, and a 0-row source skips the kernels);
- *  - otherwise it is the scan's table under the WHERE filter. */
+ *    join's output list;
+ *  - otherwise it is the scan's table under the WHERE filter.
+ * Over a materialized source (the first two) the counters stay as the node
+ * that produced the table set them — groups and joined rows are not scan
+ * rows — and a 0-row table skips the kernels. */
 struct Source {
     BkgTable* table = nullptr;
-    bool from_agg = false;
+    bool materialized = false;   /* an AggNode's or JoinNode's result table */
     BkQuerySpec q{};          /* only n_conjuncts / conjuncts are set */
 };
 static int source_of(ExecNode* node, RuntimeState* state, Source* src);
@@ -266,18 +369,12 @@ int FilterNode::fetch_chunk(RuntimeState* state) {
     if (!_opened) {
         _nrows = bkgpu_table_nrows(t);
         _ncols = bkgpu_table_ncols(t);
-        _col_types.resize(_ncols);
-        _cols_i.assign(_ncols, {});
-        _cols_d.assign(_ncols, {});
-        _cols_n.assign(_ncols, {});
-        for (int c = 0; c < _ncols; c++)
-            _col_types[c] = bkgpu_table_col_type(t, c);
+        _cols.bind(t, nullptr, _ncols);
         _scan_pos = 0;
         _opened = true;
     }
     BkQuerySpec q{};
-    q.n_conjuncts = _n_conjuncts;
-    memcpy(q.conjuncts, _conjuncts, sizeof(q.conjuncts));
+    copy_conjuncts(&q);
     if (_src_table) q = _src_q;
     const int64_t chunk = fetch_chunk_rows();
     while (_scan_pos < _nrows) {
@@ -298,49 +395,21 @@ int FilterNode::fetch_chunk(RuntimeState* state) {
         }
         _scan_pos = end;
         if (got == 0) continue;
-        for (int c = 0; c < _ncols; c++) {
-            _cols_i[c].resize(got);
-            _cols_d[c].resize(got);
-            _cols_n[c].resize(got);
-            if (bkgpu_gather(t, c, _rowids.data(), got,
-                             _cols_i[c].data(), _cols_d[c].data(),
-                             _cols_n[c].data()) != 0) {
-                state->error_msg = bkgpu_last_error();
-                return -1;
-            }
-        }
+        if (_cols.gather(state, _rowids.data(), got) < 0) return -1;
         _iter = 0;
         return 1;
     }
+    _eos_source = true;
     return 0;
 }
 
 int FilterNode::get_next(RuntimeState* state, RowBatch* batch, bool* eos) {
-    while (true) {
-        if (state->is_cancelled()) { *eos = true; return 0; }
-        if (reached_limit()) { *eos = true; return 0; }
-        if (_iter >= (int64_t)_rowids.size()) {
-            if (_eos_source) { *eos = true; return 0; }
-            int r = fetch_chunk(state);
-            if (r < 0) return r;
-            if (r == 0) { _eos_source = true; *eos = true; return 0; }
-        }
-        if (batch->is_full()) return 0;
-        auto row = std::make_unique<MemRow>(_ncols);
-        for (int c = 0; c < _ncols; c++) {
-            ExprValue v;
-            v.type = _col_types[c];
-            v.is_null_ = _cols_n[c][_iter] != 0;
-            if (!v.is_null_) {
-                if (v.type == BK_DOUBLE) v.d = _cols_d[c][_iter];
-                else v.i = _cols_i[c][_iter];
-            }
-            row->set_value(c, v);
-        }
-        batch->move_row(std::move(row));
-        _num_rows_returned++;
-        _iter++;
-    }
+    return emit_rows(state, batch, eos,
+        [&] {
+            if (_iter < (int64_t)_rowids.size()) return 1;
+            return _eos_source ? 0 : fetch_chunk(state);
+        },
+        [&](MemRow* row) { _cols.write_row(_iter++, row, 0); });
 }
 
 static ScanNode* find_scan(ExecNode* n) {
@@ -360,6 +429,51 @@ struct FetchedGroups {
     std::vector<int64_t> out_i;
     std::vector<double> out_d;
     std::vector<uint8_t> out_has;
+    /* group key k of group g: NULL iff flags bit 7-k; the key word decodes
+     * per type (bk_keyenc.h; a STRING key is its dictionary code) */
+    ExprValue key(int64_t g, int k, int32_t type) const {
+        const uint64_t e = enc[g * BK_MAX_GROUP + k];
+        return make_value(type, (flags[g] >> (7 - k)) & 1,
+                          type == BK_STRING ? (int64_t)(uint32_t)e : bk_dec_i64(e),
+                          bk_dec_f64(e));
+    }
+    /* aggregate output a of group g (agg-major) */
+    ExprValue agg(int64_t g, int a, int32_t type) const {
+        const size_t idx = (size_t)a * n + g;
+        return make_value(type, !out_has[idx], out_i[idx], out_d[idx]);
+    }
+};
+
+/* the aggregate results of a run, freed on every exit path */
+struct AggOuts {
+    std::vector<BkgAggOut*> v;
+    AggOuts() = default;
+    AggOuts(const AggOuts&) = delete;
+    AggOuts& operator=(const AggOuts&) = delete;
+    ~AggOuts() { for (auto* o : v) bkgpu_agg_free(o); }
+};
+
+/* How an AggNode's outputs come out of engine passes. Without DISTINCT there
+ * is one pass, q0 = the node's query. With DISTINCT aggs it is the
+ * reference's planner rewrite (agg_node.cpp:247-258): per distinct column j,
+ * level 1 (l1[j]) groups by (user keys + that column) and bkgpu_agg_rollup
+ * folds the dedup key out under l2[j], which holds only that column's
+ * distinct aggs. The reference's MULTI_COUNT_DISTINCT (several distinct
+ * columns) runs one such pass per column; every pass shares the same filter
+ * and group key, so the canonical-sorted group sets align row for row and
+ * the output columns stitch together. Pass 0 (q0) holds the plain aggs and
+ * always runs: it anchors the group set when a group has rows but only NULL
+ * d values, with a synthetic COUNT(*) if there is no plain agg. */
+struct PassPlan {
+    struct Src { int pass; int idx; };
+    std::vector<Src> src;             /* per aggregate: (pass, index in pass) */
+    BkQuerySpec q0{};
+    std::vector<BkQuerySpec> l1, l2;  /* per distinct column; pass 1 + j */
+    bool has_distinct() const { return !l1.empty(); }
+    /* output columns pass p fetches (at least one: the buffers are non-empty) */
+    int n_aggs(size_t p) const {
+        return std::max(1, p == 0 ? q0.n_aggs : l2[p - 1].n_aggs);
+    }
 };
 
 /* ---- AggNode (agg_node.cpp:405-587). open() drains the child pipeline —
@@ -399,29 +513,15 @@ private:
         std::vector<std::vector<uint8_t>> valid(nc, std::vector<uint8_t>(n ? n : 1, 1));
         std::vector<std::vector<int64_t>> data(nc, std::vector<int64_t>(n ? n : 1, 0));
         for (int c = 0; c < nc; c++) {
-            const bool key = c < _q.n_group;
-            const int a = c - _q.n_group;
-            const int32_t ty = key ? _q.group_types[c]
-                : bk_agg_out_type(_q.aggs[a].agg_type, _q.agg_in_types[a]);
+            const int32_t ty = slot_type(c);
             specs[c].col_type = ty;
             int32_t* d32 = (int32_t*)data[c].data();
             for (int64_t g = 0; g < n; g++) {
-                bool has;
-                int64_t vi = 0;
-                if (key) {
-                    has = !((_g.flags[g] >> (7 - c)) & 1);
-                    uint64_t e = _g.enc[g * BK_MAX_GROUP + c];
-                    if (ty == BK_DOUBLE) { double d = bk_dec_f64(e); memcpy(&vi, &d, 8); }
-                    else if (ty == BK_STRING) vi = (int64_t)(uint32_t)e;
-                    else vi = bk_dec_i64(e);
-                } else {
-                    size_t idx = (size_t)a * n + g;
-                    has = _g.out_has[idx] != 0;
-                    if (ty == BK_DOUBLE) memcpy(&vi, &_g.out_d[idx], 8);
-                    else vi = _g.out_i[idx];
-                }
-                if (!has) { vi = 0; valid[c][g] = 0; specs[c].null_frac_x1e6 = 1; }
-                if (ty == BK_STRING) d32[g] = (int32_t)vi; else data[c][g] = vi;
+                const ExprValue v = slot_value(g, c);
+                if (v.is_null()) { valid[c][g] = 0; specs[c].null_frac_x1e6 = 1; }
+                else if (ty == BK_DOUBLE) memcpy(&data[c][g], &v.d, 8);
+                else if (ty == BK_STRING) d32[g] = (int32_t)v.i;
+                else data[c][g] = v.i;
             }
         }
         _result = bkgpu_table_create(nc, specs, n);
@@ -435,13 +535,19 @@ private:
             }
         return 0;
     }
-    int run(RuntimeState* state, bool want_table) {
-        /* resolve the source first: an aggregate below is drained as a
-         * table here, so the generic child open() finds it already done */
-        Source source;
-        if (source_of(this, state, &source) < 0) return -1;
-        int ret = ExecNode::open(state);
-        if (ret < 0) return ret;
+    /* slot s of the output row: [group keys...][agg outputs...] */
+    int32_t slot_type(int s) const {
+        const int a = s - _q.n_group;
+        return a < 0 ? _q.group_types[s]
+                     : bk_agg_out_type(_q.aggs[a].agg_type, _q.agg_in_types[a]);
+    }
+    ExprValue slot_value(int64_t g, int s) const {
+        return s < _q.n_group ? _g.key(g, s, slot_type(s))
+                              : _g.agg(g, s - _q.n_group, slot_type(s));
+    }
+    /* _q = the source's filter + this node's group keys and aggregates, with
+     * the types resolved against the source table */
+    void bind_spec(const Source& source) {
         BkQuerySpec q = source.q;
         q.n_group = _desc.n_group;
         BkgTable* t = source.table;
@@ -468,138 +574,108 @@ private:
             }
         }
         _q = q;
-        int64_t expected = _desc.expected_groups > 0 ? _desc.expected_groups : 65536;
-        /* DISTINCT aggs: the reference's planner rewrite (agg_node.cpp:
-         * 247-258) — per distinct column, level 1 groups by (user keys +
-         * that column) and bkgpu_agg_rollup folds the dedup key out. The
-         * reference's MULTI_COUNT_DISTINCT (several distinct columns) runs
-         * one such pass per column; every pass shares the same filter and
-         * group key so the canonical-sorted group sets align row for row
-         * and the output columns stitch together. */
+    }
+    /* which aggregate comes from which pass, and every pass's spec */
+    int plan_passes(RuntimeState* state, BkgTable* t, PassPlan* plan) const {
+        const BkQuerySpec& q = _q;
         std::vector<int> dcols;            /* distinct columns, deduped */
         std::vector<int> agg_dcol(q.n_aggs, -1);
         for (int a = 0; a < q.n_aggs; a++) {
-            int at = q.aggs[a].agg_type;
-            if (at < BK_AGG_COUNT_DISTINCT) continue;
+            if (q.aggs[a].agg_type < BK_AGG_COUNT_DISTINCT) continue;
             int c = q.aggs[a].col;
             size_t j = 0;
             while (j < dcols.size() && dcols[j] != c) j++;
             if (j == dcols.size()) dcols.push_back(c);
             agg_dcol[a] = (int)j;
         }
-        bool has_distinct = !dcols.empty();
-        /* passes: pass 0 = plain aggs (or everything when no distinct);
-         * pass 1+j = distinct col j. src[a] = (pass, idx-in-pass). */
-        struct Src { int pass; int idx; };
-        std::vector<Src> src(q.n_aggs);
-        std::vector<BkgAggOut*> outs;
-        int64_t nrows_t = bkgpu_table_nrows(t);
-        if (source.from_agg && nrows_t == 0 && q.n_group > 0) {
-            /* no groups below: empty result, no kernel (without GROUP BY
-             * the pipeline still runs: it yields the one all-identity row) */
-            _g = FetchedGroups{};
-            _iter = 0;
-            return want_table ? upload_result(state) : 0;
+        plan->src.resize(q.n_aggs);
+        plan->q0 = q;
+        if (dcols.empty()) {
+            for (int a = 0; a < q.n_aggs; a++) plan->src[a] = {0, a};
+            return 0;
         }
-        if (!has_distinct) {
-            BkgAggOut* out = bkgpu_filter_agg(t, &q, 0, nrows_t, expected);
-            if (!out) { state->error_msg = bkgpu_last_error(); return -1; }
-            outs.push_back(out);
-            for (int a = 0; a < q.n_aggs; a++) src[a] = {0, a};
-        } else {
-            if (q.n_group > 2) {
-                state->error_msg = "DISTINCT aggs support <= 2 group keys";
-                return -1;
-            }
-            if (q.n_group == 2 && (!q.group_bits[0] || !q.group_bits[1])) {
-                /* 2 user keys + d = 3 level-1 keys: they must pack into
-                 * the two 64-bit key words via declared widths */
-                state->error_msg = "DISTINCT with 2 group keys needs "
-                                   "group_bits declared for both";
-                return -1;
-            }
-            /* pass 0: the plain aggs (always run — it also anchors the
-             * group set when a group has rows but only NULL d values) */
-            BkQuerySpec q0 = q;
-            q0.n_aggs = 0;
-            for (int a = 0; a < q.n_aggs; a++) {
-                if (agg_dcol[a] >= 0) continue;
-                src[a] = {0, q0.n_aggs};
-                q0.aggs[q0.n_aggs] = q.aggs[a];
-                q0.agg_in_types[q0.n_aggs] = q.agg_in_types[a];
-                q0.n_aggs++;
-            }
-            if (q0.n_aggs == 0) {
-                q0.aggs[0].agg_type = BK_AGG_COUNT_STAR;
-                q0.aggs[0].col = -1;
-                q0.agg_in_types[0] = BK_INT64;
-                q0.n_aggs = 1;
-            }
-            BkgAggOut* p0 = bkgpu_filter_agg(t, &q0, 0, nrows_t, expected);
-            if (!p0) { state->error_msg = bkgpu_last_error(); return -1; }
-            outs.push_back(p0);
-            for (size_t j = 0; j < dcols.size(); j++) {
-                BkQuerySpec q1 = q;
-                q1.n_group = q.n_group + 1;
-                q1.group_cols[q.n_group] = dcols[j];
-                q1.group_types[q.n_group] = bkgpu_table_col_type(t, dcols[j]);
-                q1.aggs[0].agg_type = BK_AGG_COUNT_STAR;
-                q1.aggs[0].col = -1;
-                q1.agg_in_types[0] = BK_INT64;
-                q1.n_aggs = 1;
-                /* level-2 spec: only this column's distinct aggs */
-                BkQuerySpec q2 = q;
-                q2.n_aggs = 0;
-                int32_t src_idx[BK_MAX_AGGS];
-                for (int a = 0; a < q.n_aggs; a++) {
-                    if (agg_dcol[a] != (int)j) continue;
-                    src[a] = {(int)j + 1, q2.n_aggs};
-                    src_idx[q2.n_aggs] = -1;
-                    q2.aggs[q2.n_aggs] = q.aggs[a];
-                    q2.agg_in_types[q2.n_aggs] = q.agg_in_types[a];
-                    q2.n_aggs++;
-                }
-                /* high-cardinality dedup: try the sort-based level 1 when
-                 * the (keys + d) widths are declared and pack (bkdedup.inc);
-                 * fall back to the hash path otherwise — same results */
-                BkgAggOut* l1 = nullptr;
-                if (_desc.distinct_bits > 0) {
-                    q1.group_bits[q.n_group] = _desc.distinct_bits;
-                    q1.group_base[q.n_group] = _desc.distinct_base;
-                }
-                /* high-cardinality dedup: try the sort-based level 1 (packs
-                 * via declared widths or column stats, bkdedup.inc); falls
-                 * back to the hash path when the shape does not qualify */
-                if (expected * 16 >= (1ll << 22))
-                    l1 = bkgpu_filter_agg_sorted(t, &q1, 0, nrows_t);
-                if (!l1)
-                    l1 = bkgpu_filter_agg(t, &q1, 0, nrows_t, expected * 16);
-                BkgAggOut* r = l1 ? bkgpu_agg_rollup(l1, &q2, src_idx,
-                                                     expected) : nullptr;
-                if (l1) bkgpu_agg_free(l1);
-                if (!r) {
-                    state->error_msg = bkgpu_last_error();
-                    for (auto* o : outs) bkgpu_agg_free(o);
-                    return -1;
-                }
-                outs.push_back(r);
-            }
+        if (q.n_group > 2) {
+            state->error_msg = "DISTINCT aggs support <= 2 group keys";
+            return -1;
         }
-        if (!source.from_agg) {
-            /* over a materialized aggregate the counters stay what the
-             * inner AggNode set: groups are not scan rows */
-            state->inc_num_scan_rows(nrows_t);
-            state->inc_num_filter_rows(nrows_t - bkgpu_agg_rows_passed(outs[0]));
+        if (q.n_group == 2 && (!q.group_bits[0] || !q.group_bits[1])) {
+            /* 2 user keys + d = 3 level-1 keys: they must pack into
+             * the two 64-bit key words via declared widths */
+            state->error_msg = "DISTINCT with 2 group keys needs "
+                               "group_bits declared for both";
+            return -1;
         }
-        if (want_table && !has_distinct) {
-            _result = bkgpu_agg_to_table(outs[0], t, /*canonical=*/1);
-            if (!_result) state->error_msg = bkgpu_last_error();
-            bkgpu_agg_free(outs[0]);
-            return _result ? 0 : -1;
+        /* aggregate a becomes the next output of pass `pass` under spec p */
+        auto place = [&](int a, int pass, BkQuerySpec* p) {
+            plan->src[a] = {pass, p->n_aggs};
+            p->aggs[p->n_aggs] = q.aggs[a];
+            p->agg_in_types[p->n_aggs] = q.agg_in_types[a];
+            p->n_aggs++;
+        };
+        auto count_star_only = [](BkQuerySpec* p) {
+            p->aggs[0].agg_type = BK_AGG_COUNT_STAR;
+            p->aggs[0].col = -1;
+            p->agg_in_types[0] = BK_INT64;
+            p->n_aggs = 1;
+        };
+        BkQuerySpec& q0 = plan->q0;
+        q0.n_aggs = 0;
+        for (int a = 0; a < q.n_aggs; a++)
+            if (agg_dcol[a] < 0) place(a, 0, &q0);
+        if (q0.n_aggs == 0) count_star_only(&q0);
+        for (size_t j = 0; j < dcols.size(); j++) {
+            BkQuerySpec q1 = q;
+            q1.n_group = q.n_group + 1;
+            q1.group_cols[q.n_group] = dcols[j];
+            q1.group_types[q.n_group] = bkgpu_table_col_type(t, dcols[j]);
+            if (_desc.distinct_bits > 0) {
+                q1.group_bits[q.n_group] = _desc.distinct_bits;
+                q1.group_base[q.n_group] = _desc.distinct_base;
+            }
+            count_star_only(&q1);
+            BkQuerySpec q2 = q;
+            q2.n_aggs = 0;
+            for (int a = 0; a < q.n_aggs; a++)
+                if (agg_dcol[a] == (int)j) place(a, (int)j + 1, &q2);
+            plan->l1.push_back(q1);
+            plan->l2.push_back(q2);
         }
-        /* fetch every pass in canonical key order; group sets align (same
-         * filter + same user keys), assemble the output columns */
-        int64_t n = bkgpu_agg_ngroups(outs[0]);
+        return 0;
+    }
+    /* one engine result per pass, in pass order */
+    int run_passes(RuntimeState* state, BkgTable* t, int64_t nrows_t,
+                   const PassPlan& plan, AggOuts* outs) const {
+        const int64_t expected =
+            _desc.expected_groups > 0 ? _desc.expected_groups : 65536;
+        BkgAggOut* p0 = bkgpu_filter_agg(t, &plan.q0, 0, nrows_t, expected);
+        if (!p0) { state->error_msg = bkgpu_last_error(); return -1; }
+        outs->v.push_back(p0);
+        int32_t src_idx[BK_MAX_AGGS];
+        std::fill(src_idx, src_idx + BK_MAX_AGGS, -1);
+        for (size_t j = 0; j < plan.l1.size(); j++) {
+            /* high-cardinality dedup: try the sort-based level 1 (packs
+             * via declared widths or column stats, bkdedup.inc); falls
+             * back to the hash path when the shape does not qualify —
+             * same results */
+            BkgAggOut* l1 = nullptr;
+            if (expected * 16 >= (1ll << 22))
+                l1 = bkgpu_filter_agg_sorted(t, &plan.l1[j], 0, nrows_t);
+            if (!l1)
+                l1 = bkgpu_filter_agg(t, &plan.l1[j], 0, nrows_t, expected * 16);
+            BkgAggOut* r = l1 ? bkgpu_agg_rollup(l1, &plan.l2[j], src_idx,
+                                                 expected) : nullptr;
+            if (l1) bkgpu_agg_free(l1);
+            if (!r) { state->error_msg = bkgpu_last_error(); return -1; }
+            outs->v.push_back(r);
+        }
+        return 0;
+    }
+    /* fetch every pass in canonical key order; group sets align (same
+     * filter + same user keys), assemble the output columns into _g */
+    int fetch_and_stitch(RuntimeState* state, const PassPlan& plan,
+                         const AggOuts& outs) {
+        const BkQuerySpec& q = _q;
+        int64_t n = bkgpu_agg_ngroups(outs.v[0]);
         _g.n = n;
         _g.flags.resize(n ? n : 1);
         _g.enc.resize((n ? n : 1) * BK_MAX_GROUP);
@@ -607,24 +683,20 @@ private:
         _g.out_d.resize((size_t)(n ? n : 1) * q.n_aggs);
         _g.out_has.resize((size_t)(n ? n : 1) * q.n_aggs);
         int64_t got = -1;
-        for (size_t p = 0; p < outs.size(); p++) {
-            int pn_aggs = 0;
-            for (int a = 0; a < q.n_aggs; a++)
-                if (src[a].pass == (int)p && src[a].idx + 1 > pn_aggs)
-                    pn_aggs = src[a].idx + 1;
-            if (p == 0 && pn_aggs == 0) pn_aggs = 1;  /* synthetic count(*) */
+        const std::vector<PassPlan::Src>& src = plan.src;
+        for (size_t p = 0; p < outs.v.size(); p++) {
+            const int pn_aggs = plan.n_aggs(p);
             std::vector<uint8_t> flags(n ? n : 1);
             std::vector<uint64_t> enc((n ? n : 1) * BK_MAX_GROUP);
             std::vector<int64_t> oi((size_t)(n ? n : 1) * pn_aggs);
             std::vector<double> od((size_t)(n ? n : 1) * pn_aggs);
             std::vector<uint8_t> oh((size_t)(n ? n : 1) * pn_aggs);
-            int64_t gp = bkgpu_agg_fetch(outs[p], /*sorted=*/1, n,
+            int64_t gp = bkgpu_agg_fetch(outs.v[p], /*sorted=*/1, n,
                                          flags.data(), enc.data(), oi.data(),
                                          od.data(), oh.data());
             if (gp < 0 || (p > 0 && gp != got)) {
                 state->error_msg = gp < 0 ? bkgpu_last_error()
                                           : "distinct pass group mismatch";
-                for (auto* o : outs) bkgpu_agg_free(o);
                 return -1;
             }
             if (p == 0) {
@@ -644,50 +716,53 @@ private:
                 }
             }
         }
-        for (auto* o : outs) bkgpu_agg_free(o);
         _g.n = got;
+        return 0;
+    }
+    int run(RuntimeState* state, bool want_table) {
+        /* resolve the source first: an aggregate below is drained as a
+         * table here, so the generic child open() finds it already done */
+        Source source;
+        if (source_of(this, state, &source) < 0) return -1;
+        int ret = ExecNode::open(state);
+        if (ret < 0) return ret;
+        bind_spec(source);
+        BkgTable* t = source.table;
+        const int64_t nrows_t = bkgpu_table_nrows(t);
+        _g = FetchedGroups{};
         _iter = 0;
+        if (source.materialized && nrows_t == 0 && _q.n_group > 0) {
+            /* no groups below: empty result, no kernel (without GROUP BY
+             * the pipeline still runs: it yields the one all-identity row) */
+            return want_table ? upload_result(state) : 0;
+        }
+        PassPlan plan;
+        AggOuts outs;
+        if (plan_passes(state, t, &plan) < 0 ||
+            run_passes(state, t, nrows_t, plan, &outs) < 0)
+            return -1;
+        if (!source.materialized) {
+            state->inc_num_scan_rows(nrows_t);
+            state->inc_num_filter_rows(nrows_t - bkgpu_agg_rows_passed(outs.v[0]));
+        }
+        if (want_table && !plan.has_distinct()) {
+            _result = bkgpu_agg_to_table(outs.v[0], t, /*canonical=*/1);
+            if (!_result) state->error_msg = bkgpu_last_error();
+            return _result ? 0 : -1;
+        }
+        if (fetch_and_stitch(state, plan, outs) < 0) return -1;
         return want_table ? upload_result(state) : 0;
     }
 public:
     int get_next(RuntimeState* state, RowBatch* batch, bool* eos) override {
-        while (true) {
-            if (state->is_cancelled()) { *eos = true; return 0; } /* agg_node.cpp:450 */
-            if (reached_limit() || _iter >= _g.n) { *eos = true; return 0; }
-            if (batch->is_full()) return 0;
-            auto row = std::make_unique<MemRow>(n_slots());
-            int s = 0;
-            for (int k = 0; k < _q.n_group; k++, s++) {
-                ExprValue v;
-                v.type = _q.group_types[k];
-                if ((_g.flags[_iter] >> (7 - k)) & 1) {
-                    v.is_null_ = true;
-                } else {
-                    v.is_null_ = false;
-                    uint64_t e = _g.enc[_iter * BK_MAX_GROUP + k];
-                    if (v.type == BK_DOUBLE) v.d = bk_dec_f64(e);
-                    else if (v.type == BK_STRING) v.i = (int64_t)(uint32_t)e;
-                    else v.i = bk_dec_i64(e);
-                }
-                row->set_value(s, v);
-            }
-            for (int a = 0; a < _q.n_aggs; a++, s++) {
-                ExprValue v;
-                v.type = bk_agg_out_type(_q.aggs[a].agg_type, _q.agg_in_types[a]);
-                size_t idx = (size_t)a * _g.n + _iter;
-                if (!_g.out_has[idx]) {
-                    v.is_null_ = true;
-                } else {
-                    v.is_null_ = false;
-                    if (v.type == BK_DOUBLE) v.d = _g.out_d[idx];
-                    else v.i = _g.out_i[idx];
-                }
-                row->set_value(s, v);
-            }
-            batch->move_row(std::move(row));
-            _num_rows_returned++;
-            _iter++;
-        }
+        const int ns = n_slots();
+        return emit_rows(state, batch, eos,
+            [&] { return _iter < _g.n ? 1 : 0; },
+            [&](MemRow* row) {
+                for (int s = 0; s < ns; s++)
+                    row->set_value(s, slot_value(_iter, s));
+                _iter++;
+            });
     }
     void close(RuntimeState* state) override {
         ExecNode::close(state);
@@ -695,8 +770,7 @@ public:
         _iter = 0;
         if (_result) { bkgpu_table_free(_result); _result = nullptr; }
     }
-    int n_slots() const { return _desc.n_group + _desc.n_aggs; }
-    const BkQuerySpec& spec() const { return _q; }
+    int n_slots() override { return _desc.n_group + _desc.n_aggs; }
 private:
     BkPlanNodeDesc _desc{};
     BkQuerySpec _q{};
@@ -726,6 +800,7 @@ public:
     int open(RuntimeState* state) override {
         if (!_result && run(state) < 0) return -1;
         _nrows = bkgpu_table_nrows(_result);
+        _cols.bind(_result, nullptr, n_slots());
         _pos = 0;
         _iter = 0;
         _chunk_n = 0;
@@ -735,38 +810,20 @@ public:
         if (!_result && run(state) < 0) return nullptr;
         return _result;
     }
-    int n_slots() const { return _desc.n_join_out; }
+    int n_slots() override { return _desc.n_join_out; }
     int get_next(RuntimeState* state, RowBatch* batch, bool* eos) override {
-        const int nc = n_slots();
-        while (true) {
-            if (state->is_cancelled()) { *eos = true; return 0; }
-            if (reached_limit()) { *eos = true; return 0; }
-            if (_iter >= _chunk_n) {
-                if (_pos >= _nrows) { *eos = true; return 0; }
-                if (fetch_chunk(state) < 0) return -1;
-            }
-            if (batch->is_full()) return 0;
-            auto row = std::make_unique<MemRow>(nc);
-            for (int c = 0; c < nc; c++) {
-                ExprValue v;
-                v.type = _col_types[c];
-                v.is_null_ = _cols_n[c][_iter] != 0;
-                if (!v.is_null_) {
-                    if (v.type == BK_DOUBLE) v.d = _cols_d[c][_iter];
-                    else v.i = _cols_i[c][_iter];
-                }
-                row->set_value(c, v);
-            }
-            batch->move_row(std::move(row));
-            _num_rows_returned++;
-            _iter++;
-        }
+        return emit_rows(state, batch, eos,
+            [&] {
+                if (_iter < _chunk_n) return 1;
+                return _pos < _nrows ? fetch_chunk(state) : 0;
+            },
+            [&](MemRow* row) { _cols.write_row(_iter++, row, 0); });
     }
     void close(RuntimeState* state) override {
         ExecNode::close(state);
         if (_result) { bkgpu_table_free(_result); _result = nullptr; }
-        _rowids.clear();
-        _cols_i.clear(); _cols_d.clear(); _cols_n.clear();
+        release(_rowids);
+        _cols.clear();
         _nrows = _pos = _iter = _chunk_n = 0;
     }
 private:
@@ -775,9 +832,7 @@ private:
                        BkQuerySpec* q) {
         if (n->node_type() == BK_TABLE_FILTER_NODE ||
             n->node_type() == BK_WHERE_FILTER_NODE) {
-            FilterNode* f = static_cast<FilterNode*>(n);
-            q->n_conjuncts = f->n_conjuncts();
-            memcpy(q->conjuncts, f->conjuncts(), sizeof(q->conjuncts));
+            static_cast<FilterNode*>(n)->copy_conjuncts(q);
             n = n->children().empty() ? nullptr : n->children()[0];
         }
         if (!n || n->node_type() != BK_SCAN_NODE) {
@@ -816,37 +871,23 @@ private:
         state->inc_num_scan_rows(no + bkgpu_table_nrows(inner));
         int64_t st[8];
         if (bkgpu_join_stats(st) == 0) state->inc_num_filter_rows(no - st[0]);
-        _col_types.resize(n_slots());
-        for (int c = 0; c < n_slots(); c++)
-            _col_types[c] = bkgpu_table_col_type(_result, c);
         return 0;
     }
+    /* the next fetch_chunk_rows() result rows; 1 = chunk ready */
     int fetch_chunk(RuntimeState* state) {
-        const int nc = n_slots();
         const int64_t n = std::min(_nrows - _pos, fetch_chunk_rows());
         _rowids.resize(n);
         for (int64_t i = 0; i < n; i++) _rowids[i] = _pos + i;
-        _cols_i.assign(nc, {}); _cols_d.assign(nc, {}); _cols_n.assign(nc, {});
-        for (int c = 0; c < nc; c++) {
-            _cols_i[c].resize(n); _cols_d[c].resize(n); _cols_n[c].resize(n);
-            if (bkgpu_gather(_result, c, _rowids.data(), n, _cols_i[c].data(),
-                             _cols_d[c].data(), _cols_n[c].data()) != 0) {
-                state->error_msg = bkgpu_last_error();
-                return -1;
-            }
-        }
+        if (_cols.gather(state, _rowids.data(), n) < 0) return -1;
         _pos += n;
         _chunk_n = n;
         _iter = 0;
-        return 0;
+        return 1;
     }
     BkPlanNodeDesc _desc{};
     BkgTable* _result = nullptr;
-    std::vector<int32_t> _col_types;
     std::vector<int64_t> _rowids;
-    std::vector<std::vector<int64_t>> _cols_i;
-    std::vector<std::vector<double>> _cols_d;
-    std::vector<std::vector<uint8_t>> _cols_n;
+    HostCols _cols;
     int64_t _nrows = 0, _pos = 0, _iter = 0, _chunk_n = 0;
 };
 
@@ -874,39 +915,26 @@ static int source_of(ExecNode* node, RuntimeState* state, Source* src) {
         } else if (is_agg_node(n)) {
             src->table = static_cast<AggNode*>(n)->result_table(state);
             if (!src->table) return -1;
-            src->from_agg = true;
+            src->materialized = true;
             src->q.n_conjuncts = n_having;
             memcpy(src->q.conjuncts, having, sizeof(BkConjunct) * n_having);
             return 0;
-        } else if (ty == BK_JOIN_NODE) {
-            /* the joined table; columns above are output-list positions. A
-             * WHERE between the node and the join filters joined rows (how a
-             * non-equi ON condition is applied). Counters stay as the
-             * JoinNode set them, as over an aggregate. */
+        } else if (ty == BK_JOIN_NODE || ty == BK_SCAN_NODE) {
             if (n_having) {
                 state->error_msg = "HAVING_FILTER_NODE without an aggregate below";
                 return -1;
             }
-            src->table = static_cast<JoinNode*>(n)->result_table(state);
-            if (!src->table) return -1;
-            src->from_agg = true;
-            if (where) {
-                src->q.n_conjuncts = where->n_conjuncts();
-                memcpy(src->q.conjuncts, where->conjuncts(),
-                       sizeof(src->q.conjuncts));
+            if (ty == BK_JOIN_NODE) {
+                /* the joined table; columns above are output-list positions.
+                 * A WHERE between the node and the join filters joined rows
+                 * (how a non-equi ON condition is applied). */
+                src->table = static_cast<JoinNode*>(n)->result_table(state);
+                if (!src->table) return -1;
+                src->materialized = true;
+            } else {
+                src->table = static_cast<ScanNode*>(n)->table();
             }
-            return 0;
-        } else if (ty == BK_SCAN_NODE) {
-            if (n_having) {
-                state->error_msg = "HAVING_FILTER_NODE without an aggregate below";
-                return -1;
-            }
-            src->table = static_cast<ScanNode*>(n)->table();
-            if (where) {
-                src->q.n_conjuncts = where->n_conjuncts();
-                memcpy(src->q.conjuncts, where->conjuncts(),
-                       sizeof(src->q.conjuncts));
-            }
+            if (where) where->copy_conjuncts(&src->q);
             return 0;
         }
     }
@@ -940,7 +968,7 @@ int FilterNode::open(RuntimeState* state) {
          * over the aggregate's materialized table */
         Source source;
         if (source_of(this, state, &source) < 0) return -1;
-        if (!source.from_agg ||
+        if (!source.materialized ||
             source.q.n_conjuncts + _n_conjuncts > BK_MAX_CONJUNCTS) {
             state->error_msg = "HAVING_FILTER_NODE: bad plan below";
             return -1;
@@ -978,75 +1006,37 @@ public:
         int64_t limit = _limit > 0 ? _limit : bkgpu_table_nrows(t);
         _rowids.resize(limit > 0 ? limit : 1);
         int64_t got = 0;
-        if (!(source.from_agg && bkgpu_table_nrows(t) == 0))
+        if (!(source.materialized && bkgpu_table_nrows(t) == 0))
             got = bkgpu_sort_topk(t, &q, _desc.order, _desc.n_order, 0,
                                   bkgpu_table_nrows(t), limit, _rowids.data());
         if (got < 0) { state->error_msg = bkgpu_last_error(); return -1; }
         _rowids.resize(got);
-        if (!source.from_agg) state->inc_num_scan_rows(bkgpu_table_nrows(t));
+        if (!source.materialized) state->inc_num_scan_rows(bkgpu_table_nrows(t));
         /* materialize out_cols */
-        _cols_i.assign(_desc.n_out_cols, {});
-        _cols_d.assign(_desc.n_out_cols, {});
-        _cols_n.assign(_desc.n_out_cols, {});
-        _col_types.resize(_desc.n_out_cols);
-        for (int c = 0; c < _desc.n_out_cols; c++) {
-            int col = _desc.out_cols[c];
-            _col_types[c] = bkgpu_table_col_type(t, col);
-            _cols_i[c].resize(got ? got : 1);
-            _cols_d[c].resize(got ? got : 1);
-            _cols_n[c].resize(got ? got : 1);
-            if (got > 0 &&
-                bkgpu_gather(t, col, _rowids.data(), got, _cols_i[c].data(),
-                             _cols_d[c].data(), _cols_n[c].data()) != 0) {
-                state->error_msg = bkgpu_last_error();
-                return -1;
-            }
-        }
+        _cols.bind(t, _desc.out_cols, _desc.n_out_cols);
+        if (_cols.gather(state, _rowids.data(), got) < 0) return -1;
         _iter = 0;
         return 0;
     }
     int get_next(RuntimeState* state, RowBatch* batch, bool* eos) override {
-        while (true) {
-            if (state->is_cancelled()) { *eos = true; return 0; }
-            if (reached_limit() || _iter >= (int64_t)_rowids.size()) {
-                *eos = true;
-                return 0;
-            }
-            if (batch->is_full()) return 0;
-            auto row = std::make_unique<MemRow>(n_slots());
-            for (int c = 0; c < _desc.n_out_cols; c++) {
-                ExprValue v;
-                v.type = _col_types[c];
-                v.is_null_ = _cols_n[c][_iter] != 0;
-                if (!v.is_null_) {
-                    if (v.type == BK_DOUBLE) v.d = _cols_d[c][_iter];
-                    else v.i = _cols_i[c][_iter];
-                }
-                row->set_value(c, v);
-            }
-            batch->move_row(std::move(row));
-            _num_rows_returned++;
-            _iter++;
-        }
+        return emit_rows(state, batch, eos,
+            [&] { return _iter < (int64_t)_rowids.size() ? 1 : 0; },
+            [&](MemRow* row) { _cols.write_row(_iter++, row, 0); });
     }
     void close(RuntimeState* state) override {
         ExecNode::close(state);
-        _rowids.clear();
+        release(_rowids);
+        _cols.clear();
         _iter = 0;
     }
-    int n_slots() const { return _desc.n_out_cols; }
-    const std::vector<int32_t>& col_types() const { return _col_types; }
+    int n_slots() override { return _desc.n_out_cols; }
 private:
     BkPlanNodeDesc _desc{};
-    std::vector<int64_t> _rowids;
-    std::vector<std::vector<int64_t>> _cols_i;
-    std::vector<std::vector<double>> _cols_d;
-    std::vector<std::vector<uint8_t>> _cols_n;
-    std::vector<int32_t> _col_types;
+    std::vector<int64_t> _rowids;      /* the selected rows, final order */
+    HostCols _cols;
     int64_t _iter = 0;
 };
 
-/* ---- LimitNode ---- */
 /* ---- WindowNode (window_node.cpp, NON-FRAME mode; fns evaluated by
  * bkgpu_window over rows sorted by (partition, order, arrival)). Slots:
  * [out_cols...][window fn outputs...]. ---- */
@@ -1084,7 +1074,7 @@ public:
         _win_d.resize((size_t)_desc.n_winfns * (nrows ? nrows : 1));
         _win_n.resize((size_t)_desc.n_winfns * (nrows ? nrows : 1));
         int64_t got = 0;
-        if (!(source.from_agg && nrows == 0))
+        if (!(source.materialized && nrows == 0))
             got = bkgpu_window(t, &q, _desc.part_col, _desc.order,
                                _desc.n_order, _desc.winfns, _desc.n_winfns,
                                _desc.frame_mode,
@@ -1094,7 +1084,7 @@ public:
                                _win_d.data(), _win_n.data());
         if (got < 0) { state->error_msg = bkgpu_last_error(); return -1; }
         _n = got;
-        if (!source.from_agg) {
+        if (!source.materialized) {
             state->inc_num_scan_rows(nrows);
             state->inc_num_filter_rows(nrows - got);
         }
@@ -1102,84 +1092,57 @@ public:
         for (int f = 0; f < _desc.n_winfns; f++)
             _fn_types[f] = fn_out_type(_desc.winfns[f], t);
         /* materialize out_cols of the sorted rows */
-        _cols_i.assign(_desc.n_out_cols, {});
-        _cols_d.assign(_desc.n_out_cols, {});
-        _cols_n.assign(_desc.n_out_cols, {});
-        _col_types.resize(_desc.n_out_cols);
-        for (int c = 0; c < _desc.n_out_cols; c++) {
-            int col = _desc.out_cols[c];
-            _col_types[c] = bkgpu_table_col_type(t, col);
-            _cols_i[c].resize(_n ? _n : 1);
-            _cols_d[c].resize(_n ? _n : 1);
-            _cols_n[c].resize(_n ? _n : 1);
-            if (_n > 0 &&
-                bkgpu_gather(t, col, _rowids.data(), _n, _cols_i[c].data(),
-                             _cols_d[c].data(), _cols_n[c].data()) != 0) {
-                state->error_msg = bkgpu_last_error();
-                return -1;
-            }
-        }
+        _cols.bind(t, _desc.out_cols, _desc.n_out_cols);
+        if (_cols.gather(state, _rowids.data(), _n) < 0) return -1;
         _iter = 0;
         return 0;
     }
     int get_next(RuntimeState* state, RowBatch* batch, bool* eos) override {
-        while (true) {
-            if (state->is_cancelled()) { *eos = true; return 0; }
-            if (reached_limit() || _iter >= _n) { *eos = true; return 0; }
-            if (batch->is_full()) return 0;
-            auto row = std::make_unique<MemRow>(n_slots());
-            int s = 0;
-            for (int c = 0; c < _desc.n_out_cols; c++, s++) {
-                ExprValue v;
-                v.type = _col_types[c];
-                v.is_null_ = _cols_n[c][_iter] != 0;
-                if (!v.is_null_) {
-                    if (v.type == BK_DOUBLE) v.d = _cols_d[c][_iter];
-                    else v.i = _cols_i[c][_iter];
+        return emit_rows(state, batch, eos,
+            [&] { return _iter < _n ? 1 : 0; },
+            [&](MemRow* row) {
+                _cols.write_row(_iter, row, 0);
+                for (int f = 0; f < _desc.n_winfns; f++) {
+                    size_t idx = (size_t)f * _n + _iter;
+                    row->set_value(_desc.n_out_cols + f,
+                                   make_value(_fn_types[f], _win_n[idx] != 0,
+                                              _win_i[idx], _win_d[idx]));
                 }
-                row->set_value(s, v);
-            }
-            for (int f = 0; f < _desc.n_winfns; f++, s++) {
-                ExprValue v;
-                v.type = _fn_types[f];
-                size_t idx = (size_t)f * _n + _iter;
-                v.is_null_ = _win_n[idx] != 0;
-                if (!v.is_null_) {
-                    if (v.type == BK_DOUBLE) v.d = _win_d[idx];
-                    else v.i = _win_i[idx];
-                }
-                row->set_value(s, v);
-            }
-            batch->move_row(std::move(row));
-            _num_rows_returned++;
-            _iter++;
-        }
+                _iter++;
+            });
     }
     void close(RuntimeState* state) override {
         ExecNode::close(state);
-        _rowids.clear(); _win_i.clear(); _win_d.clear(); _win_n.clear();
+        release(_rowids);
+        release(_win_i);
+        release(_win_d);
+        release(_win_n);
+        release(_fn_types);
+        _cols.clear();
         _iter = 0; _n = 0;
     }
-    int n_slots() const { return _desc.n_out_cols + _desc.n_winfns; }
+    int n_slots() override { return _desc.n_out_cols + _desc.n_winfns; }
 
 private:
     BkPlanNodeDesc _desc{};
-    std::vector<int64_t> _rowids;
-    std::vector<int64_t> _win_i;
+    std::vector<int64_t> _rowids;      /* rows sorted by (partition, order) */
+    std::vector<int64_t> _win_i;       /* fn outputs, fn-major */
     std::vector<double> _win_d;
     std::vector<uint8_t> _win_n;
     std::vector<int32_t> _fn_types;
-    std::vector<std::vector<int64_t>> _cols_i;
-    std::vector<std::vector<double>> _cols_d;
-    std::vector<std::vector<uint8_t>> _cols_n;
-    std::vector<int32_t> _col_types;
+    HostCols _cols;
     int64_t _iter = 0, _n = 0;
 };
 
+/* ---- LimitNode (limit_node.cpp): passes the child's rows on, minus the
+ * first _offset, up to _limit. ---- */
 class LimitNode : public ExecNode {
     int64_t _offset = 0;
     int64_t _num_rows_skipped = 0;
 public:
+    int n_slots() override {
+        return _children.empty() ? 0 : _children[0]->n_slots();
+    }
     int init(const BkPlanNodeDesc& node) override {
         ExecNode::init(node);
         _offset = node.offset;
@@ -1277,24 +1240,7 @@ struct BkExecTree {
 };
 
 static int tree_n_slots(const BkExecTree* t) {
-    using namespace bkexec;
-    ExecNode* n = t->root;
-    while (n && n->node_type() == BK_LIMIT_NODE && !n->children().empty())
-        n = n->children()[0];
-    if (!n) return 0;
-    if (n->node_type() == BK_AGG_NODE || n->node_type() == BK_MERGE_AGG_NODE)
-        return static_cast<AggNode*>(n)->n_slots();
-    if (n->node_type() == BK_SORT_NODE)
-        return static_cast<SortNode*>(n)->n_slots();
-    if (n->node_type() == BK_WINDOW_NODE)
-        return static_cast<WindowNode*>(n)->n_slots();
-    if (n->node_type() == BK_JOIN_NODE)
-        return static_cast<JoinNode*>(n)->n_slots();
-    if (n->node_type() == BK_TABLE_FILTER_NODE ||
-        n->node_type() == BK_WHERE_FILTER_NODE ||
-        n->node_type() == BK_HAVING_FILTER_NODE)   /* slots of the AGG below */
-        return static_cast<FilterNode*>(n)->n_slots();
-    return 0;
+    return t->root ? t->root->n_slots() : 0;
 }
 
 extern "C" BkExecTree* bkexec_create_tree(const BkPlanNodeDesc* nodes, int n_nodes) {
