@@ -14,6 +14,25 @@ from .plan import TYPE_INT64, TYPE_DOUBLE, TYPE_STRING
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = os.path.join(_HERE, "libbkgpu.so")
 
+# BkFrameMode (include/bk_common.h)
+(BK_FRAME_NONE, BK_FRAME_ROWS, BK_FRAME_RANGE_UPC, BK_FRAME_RANGE_CRF,
+ BK_FRAME_RANGE_VALUE) = range(5)
+
+
+def frame_args(frame):
+    """A window call's frame argument -> (BkFrameMode, pre, fol): None,
+    (pre, fol) rows, "range_upc", "range_crf" or ("range_val", pre, fol);
+    a negative bound is UNBOUNDED."""
+    if frame is None:
+        return BK_FRAME_NONE, -1, -1
+    if frame == "range_upc":    # RANGE UNBOUNDED PRECEDING..CURRENT ROW
+        return BK_FRAME_RANGE_UPC, -1, -1
+    if frame == "range_crf":    # RANGE CURRENT ROW..UNBOUNDED FOLLOWING
+        return BK_FRAME_RANGE_CRF, -1, -1
+    if isinstance(frame, tuple) and frame and frame[0] == "range_val":
+        return BK_FRAME_RANGE_VALUE, frame[1], frame[2]
+    return BK_FRAME_ROWS, frame[0], frame[1]
+
 
 def substr_ref(w: str, start: int, ln=None) -> str:
     """SQL SUBSTR exactly as /root/reference/src/expr/internal_functions.cpp
@@ -126,14 +145,6 @@ def _load():
     lib.bkgpu_agg_empty.argtypes = [C.POINTER(BkQuerySpec), C.c_int64]
     lib.bkgpu_agg_nfilled.restype = C.c_int64
     lib.bkgpu_agg_nfilled.argtypes = [C.c_void_p]
-    lib.bkgpu_window.restype = C.c_int64
-    lib.bkgpu_window.argtypes = [C.c_void_p, C.POINTER(BkQuerySpec), C.c_int32,
-                                 C.POINTER(BkOrderSpec), C.c_int,
-                                 C.POINTER(BkWindowFn), C.c_int,
-                                 C.c_int32, C.c_int64, C.c_int64,
-                                 C.c_int64, C.c_int64,
-                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64),
-                                 C.POINTER(C.c_double), C.POINTER(C.c_uint8)]
     lib.bkgpu_window_multi.restype = C.c_int64
     lib.bkgpu_window_multi.argtypes = [C.c_void_p, C.POINTER(BkQuerySpec),
                                  C.POINTER(C.c_int32), C.c_int32,
@@ -651,30 +662,15 @@ class GpuEngine:
         out_i = np.zeros(len(fns) * cap, dtype=np.int64)
         out_d = np.zeros(len(fns) * cap, dtype=np.float64)
         out_null = np.zeros(len(fns) * cap, dtype=np.uint8)
-        if frame is None:
-            fr, fpre, ffol = 0, -1, -1
-        elif frame == "range_upc":    # RANGE UNBOUNDED PRECEDING..CURRENT ROW
-            fr, fpre, ffol = 2, -1, -1
-        elif frame == "range_crf":    # RANGE CURRENT ROW..UNBOUNDED FOLLOWING
-            fr, fpre, ffol = 3, -1, -1
-        elif isinstance(frame, tuple) and frame[0] == "range_val":
-            fr, fpre, ffol = 4, frame[1], frame[2]
-        else:
-            fr, fpre, ffol = 1, frame[0], frame[1]
-        if isinstance(part_col, (list, tuple)):
-            parr = (C.c_int32 * max(len(part_col), 1))(*part_col)
-            n = self.lib.bkgpu_window_multi(
-                table.handle, C.byref(q), parr, len(part_col), oarr,
-                len(order), farr, len(fns), fr, fpre, ffol, row_begin,
-                row_end,
-                rowids.ctypes.data_as(C.POINTER(C.c_int64)),
-                out_i.ctypes.data_as(C.POINTER(C.c_int64)),
-                out_d.ctypes.data_as(C.POINTER(C.c_double)),
-                out_null.ctypes.data_as(C.POINTER(C.c_uint8)))
-        else:
-            n = self.lib.bkgpu_window(
-                table.handle, C.byref(q), part_col, oarr, len(order),
-                farr, len(fns), fr, fpre, ffol, row_begin, row_end,
+        mode, fpre, ffol = frame_args(frame)
+        # one partition column or none (any negative int) is the short form
+        # of a PARTITION BY list
+        if not isinstance(part_col, (list, tuple)):
+            part_col = [part_col] if part_col >= 0 else []
+        parr = (C.c_int32 * max(len(part_col), 1))(*part_col)
+        n = self.lib.bkgpu_window_multi(
+            table.handle, C.byref(q), parr, len(part_col), oarr,
+            len(order), farr, len(fns), mode, fpre, ffol, row_begin, row_end,
             rowids.ctypes.data_as(C.POINTER(C.c_int64)),
             out_i.ctypes.data_as(C.POINTER(C.c_int64)),
             out_d.ctypes.data_as(C.POINTER(C.c_double)),

@@ -7,7 +7,7 @@ import ctypes as C
 
 import numpy as np
 
-from .engine import _load
+from .engine import _load, frame_args
 from .plan import (BkQuerySpec, BkConjunct, BkAggSpec, BkOrderSpec,  # noqa
                    BkWindowFn, _WINFNS,
                    BK_MAX_GROUP, BK_MAX_CONJ, BK_MAX_AGGS, _OPS, _AGGS,
@@ -137,14 +137,7 @@ def window_node(part_col, order, fns, out_cols, num_children=1, limit=-1,
     d.n_out_cols = len(out_cols)
     for i, c in enumerate(out_cols):
         d.out_cols[i] = c
-    if frame == "range_upc":
-        d.frame_mode = 2
-    elif frame == "range_crf":
-        d.frame_mode = 3
-    elif isinstance(frame, tuple) and frame and frame[0] == "range_val":
-        d.frame_mode, d.frame_pre, d.frame_fol = 4, frame[1], frame[2]
-    elif frame is not None:
-        d.frame_mode, d.frame_pre, d.frame_fol = 1, frame[0], frame[1]
+    d.frame_mode, d.frame_pre, d.frame_fol = frame_args(frame)
     return d
 
 

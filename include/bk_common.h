@@ -299,6 +299,20 @@ typedef enum BkWinType {
     BK_WIN_NTILE        = 20,   /* param = n buckets */
 } BkWinType;
 
+/* window frame of a call (the frame_rows / frame_mode argument). pre/fol
+ * bounds: negative = UNBOUNDED, 0 = CURRENT ROW. */
+typedef enum BkFrameMode {
+    BK_FRAME_NONE        = 0,   /* non-frame: every fn sees its whole partition */
+    BK_FRAME_ROWS        = 1,   /* ROWS BETWEEN pre PRECEDING AND fol FOLLOWING */
+    BK_FRAME_RANGE_UPC   = 2,   /* RANGE UNBOUNDED PRECEDING..CURRENT ROW: ends
+                                   with the current row's peer group */
+    BK_FRAME_RANGE_CRF   = 3,   /* RANGE CURRENT ROW..UNBOUNDED FOLLOWING:
+                                   starts at the current row's peer-group head */
+    BK_FRAME_RANGE_VALUE = 4,   /* RANGE BETWEEN pre PRECEDING AND fol FOLLOWING
+                                   by value of the single ASC integer order
+                                   key; NULL-key rows frame their peer group */
+} BkFrameMode;
+
 typedef struct BkWindowFn {
     int32_t fn_type;   /* BkWinType */
     int32_t col;       /* input column, -1 for COUNT_STAR / pure rank fns */

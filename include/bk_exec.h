@@ -69,9 +69,10 @@ typedef struct BkPlanNodeDesc {
     int32_t     out_cols[BK_MAX_COLS];
     /* WINDOW_NODE payload (window_node.cpp); reuses n_order/order for the
      * in-partition sort and n_out_cols/out_cols for the materialized input
-     * columns. frame_mode: 0 non-frame, 1 ROWS [f_pre PRECEDING, f_fol
-     * FOLLOWING] (negative = UNBOUNDED), 2 RANGE UNBOUNDED..CURRENT,
-     * 3 RANGE CURRENT..UNBOUNDED (see bkgpu_window). */
+     * columns. frame_mode: a BkFrameMode (bk_common.h) — BK_FRAME_NONE,
+     * BK_FRAME_ROWS [frame_pre PRECEDING, frame_fol FOLLOWING] (negative =
+     * UNBOUNDED), BK_FRAME_RANGE_UPC, BK_FRAME_RANGE_CRF or
+     * BK_FRAME_RANGE_VALUE (see bkgpu_window). */
     int32_t     part_col;            /* -1 = single whole-set partition */
     int32_t     n_winfns;
     BkWindowFn  winfns[BK_MAX_WINFNS];

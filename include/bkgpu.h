@@ -280,10 +280,14 @@ int64_t bkgpu_sort_topk(BkgTable* t, const BkQuerySpec* q,
                         int64_t limit, int64_t* out_rows);
 double bkgpu_topk_kernel_ms(void);
 
-/* ---- window functions (WindowNode, window_node.cpp; non-frame mode and
- * ROWS frames — frame_rows=1, bounds f_pre/f_fol rows, negative =
- * UNBOUNDED; RowFrameWindowProcessor semantics for SUM/COUNT/AVG and
- * FIRST/LAST/NTH_VALUE): rows sorted by (partition, order, arrival);
+/* ---- window functions (WindowNode, window_node.cpp). frame_rows is a
+ * BkFrameMode (bk_common.h): BK_FRAME_NONE (whole partition),
+ * BK_FRAME_ROWS (f_pre/f_fol rows), BK_FRAME_RANGE_UPC (UNBOUNDED
+ * PRECEDING..CURRENT ROW), BK_FRAME_RANGE_CRF (CURRENT ROW..UNBOUNDED
+ * FOLLOWING), BK_FRAME_RANGE_VALUE (f_pre/f_fol by value of one ASC integer
+ * order key); a negative bound = UNBOUNDED. Frames follow the
+ * Row/RangeFrameWindowProcessor semantics for SUM/COUNT/AVG/MIN/MAX and
+ * FIRST/LAST/NTH_VALUE. Rows sorted by (partition, order, arrival);
  * outputs fn-major host arrays out_i/out_d/out_null[f*n + i]; out_rowids
  * receives the sorted global row ids. Returns rows produced, <0 error. ---- */
 int64_t bkgpu_window(BkgTable* t, const BkQuerySpec* q, int32_t part_col,

@@ -694,6 +694,110 @@ def test_gpu_range_val_parity(eng, orc, vframe):
     assert np.all(d[mask] <= tol[mask])
 
 
+_TABLES = {}
+
+
+def gpu_vs_oracle(eng, orc, specs, n, seed, fns, part_col, order, frame=None):
+    """One engine window call and the oracle's answer on the same seeded
+    table (generated once per (specs, n, seed)); asserts the frame tests'
+    comparison block and returns the oracle result for case-shape checks."""
+    t = eng.create_table(specs, n)
+    try:
+        eng.generate(t, seed)
+        got = eng.window(t, fns, part_col=part_col, order=order, frame=frame)
+    finally:
+        t.free()
+    key = (tuple(specs), n, seed)
+    if key not in _TABLES:
+        _TABLES[key] = gen(orc, specs, n, seed)
+    cols, valids, types = _TABLES[key]
+    exp = orc.window(cols, valids, types,
+                     [(W[f[0]], f[1], f[2] if len(f) > 2 else 0,
+                       f[3] if len(f) > 3 else None) for f in fns],
+                     part_col=part_col, order=order, frame=frame)
+    assert got["n"] == exp["n"]
+    assert np.array_equal(got["rowids"], exp["rowids"])
+    assert np.array_equal(got["out_null"], exp["out_null"])
+    assert np.array_equal(got["out_i"], exp["out_i"])
+    mask = exp["out_null"] == 0
+    d = np.abs(got["out_d"] - exp["out_d"])
+    tol = 1e-9 * (np.abs(exp["out_d"]) + 100)
+    assert np.all(d[mask] <= tol[mask])
+    return exp
+
+
+NULLY_SPECS = [(TYPE_INT64, D_UNI, 0, 8, 0),
+               (TYPE_INT64, D_UNI, 0, 50, 100_000),
+               (TYPE_INT64, D_UNI, -500, 500, 850_000),
+               (TYPE_DOUBLE, D_SUM16, 0, 0, 850_000),
+               (TYPE_STRING, D_DICT, 64, 0, 850_000)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("order", [[(1, 1, 1)], [(1, 1, 0)]])
+@pytest.mark.parametrize("frame", [(1, 1), (3, 4)])
+def test_gpu_rows_frame_mostly_null_values(eng, orc, frame, order):
+    """85%-NULL value columns: frames with no value (NULL result) next to
+    frames with some, for every aggregate family incl. STRING MIN/MAX. The
+    (3, 4) frame is 8 rows long: the sparse-table level on an exact power of
+    two."""
+    fns = [("sum", 2), ("min", 2), ("max", 3), ("avg", 3), ("min", 4),
+           ("max", 4), ("count", 2), ("first_value", 4)]
+    exp = gpu_vs_oracle(eng, orc, NULLY_SPECS, 4000, 101, fns, 0, order, frame)
+    for f in range(6):    # SUM/MIN/MAX/AVG: NULL and non-NULL results both occur
+        nulls = int(exp["out_null"][f].sum())
+        assert 0 < nulls < exp["n"], (fns[f], nulls)
+    assert not exp["out_null"][6].any()   # COUNT is never NULL
+
+
+EDGE64_SPECS = [(TYPE_INT64, D_UNI, 0, 4, 0),
+                (TYPE_INT64, D_UNI, 0, 1 << 40, 0),
+                (TYPE_INT64, D_UNI, 0, 1 << 40, 100_000),
+                (TYPE_DOUBLE, D_SUM16, 0, 0, 100_000)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("frame,longest", [((31, 32), 64), ((32, 32), 65)])
+def test_gpu_rows_frame_direct_sum_boundary(eng, orc, frame, longest):
+    """Either side of the 64-row rule of the frame SUM/AVG evaluator: full
+    64-row frames are summed in frame order, 65-row frames take the prefix
+    difference; partition edges give shorter frames in both cases."""
+    fns = [("avg", 2), ("sum", 3), ("count_star", -1)]
+    exp = gpu_vs_oracle(eng, orc, EDGE64_SPECS, 3000, 102, fns, 0, [(1, 1, 1)],
+                        frame)
+    rows = exp["out_i"][2]
+    assert rows.max() == longest
+    assert rows.min() < longest
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("null_first", [1, 0])
+def test_gpu_range_val_null_keys_either_end(eng, orc, null_first):
+    """RANGE by value with the NULL order keys sorted first or last: the
+    non-null span the binary searches run over is clipped at either end."""
+    specs = [(TYPE_INT64, D_UNI, 0, 6, 0),
+             (TYPE_INT64, D_UNI, 0, 300, 200_000),
+             (TYPE_INT64, D_UNI, -40, 40, 300_000)]
+    fns = [("count_star", -1), ("min", 2), ("sum", 2), ("avg", 2)]
+    exp = gpu_vs_oracle(eng, orc, specs, 3000, 103, fns, 0,
+                        [(1, 1, null_first)], ("range_val", 7, 0))
+    rows = exp["out_i"][0]
+    assert rows.min() == 1 and rows.max() > 64   # both AVG sum routes
+
+
+@pytest.mark.gpu
+def test_gpu_window_eight_fns_all_families(eng, orc):
+    """BK_MAX_WINFNS fns in one non-frame call, one per family, LEAD with a
+    float default on a DOUBLE column. Ordered by the nullable c2, so each
+    partition's NULL keys form one large peer group."""
+    fns = [("count_star", -1), ("sum", 3), ("min", 2), ("dense_rank", -1),
+           ("cume_dist", -1), ("ntile", -1, 7), ("nth_value", 2, 3),
+           ("lead", 3, 2, 0.5)]
+    exp = gpu_vs_oracle(eng, orc, EDGE64_SPECS, 3000, 102, fns, 0,
+                        [(2, 1, 1), (0, 1, 1)])
+    assert exp["out_i"][3].max() < exp["out_i"][0].max()   # peers not singletons
+
+
 @pytest.mark.gpu
 def test_gpu_window_empty_selection(eng, orc):
     """WHERE eliminates every row: window returns 0 rows cleanly."""
